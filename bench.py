@@ -15,8 +15,15 @@ perturbed by 8*randn).  Batches shard across GPUs with no data-path collective.
   --scaling strong  --batch images in total, rank r owns its contiguous slice (B = 256 over N GPUs)
   --gather MODE     additionally time the reassembly of the outputs on every rank (never part of `value`):
                     all_gather | p2p (direct peer exchange) | chunked (compute and exchange overlapped, 4 sub-batches)
+  --dump-outputs D  write the last timed step's y, grad wrt x and grad wrt M (rank 0) to D/<name>.npy, float32; the inputs are
+                    seeded, so two builds run with the same arguments can be compared output for output
+  --full            also measure what the keys below hold; a plain run only sets up, settles (untimed, 3-15 s: first touch of the
+                    allocations), runs --warmup steps, times EXACTLY --steps steps (ms_per_step = their wall time / --steps), dumps
+                    and prints the headline keys
 
-The JSON line carries
+With --full the JSON line also carries
+  ms_per_step_*  after the headline: --groups groups of --steps steps (median, IQR, every group), rotated-input groups
+                 interleaved with one-input-set groups; the settle's trace; device clocks before and after
   roofline       the dominant public op of the step (HIP-event timed through the C ABI on the launch stream) against its
                  ALGORITHMIC bytes per SURVEY.md 8(d): warp fwd 2e, blur fwd 2e, blur bwd 2e, warp bwd 3e per element;
                  `kernels` holds every launch with the bytes that launch itself must move
@@ -99,12 +106,18 @@ def parse_args():
     p.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     p.add_argument("--gather", choices=("none", "all_gather", "p2p", "chunked"), default="none",
                    help="also time the reassembly of the outputs on every rank (reported separately)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="skip other_configs / generic_gpu (profiling runs)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also measure everything else the JSON line can carry: settle + --groups timed groups, "
+                        "one-input-set groups, clocks, per-launch roofline, streaming copy, generic_gpu, other_configs, cpu_baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (y, grad wrt x, grad wrt M) as DIR/<name>.npy in float32; an array "
+                        "above 16 MB is stored as a fixed, seeded sample of its flattened elements")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip other_configs / generic_gpu (profiling runs)")
     p.add_argument("--cpu-batch", type=int, default=8, help="images in the CPU baseline sample")
     p.add_argument("--groups", type=int, default=9,
-                   help="timed groups of --steps steps each (every group bracketed by barrier + synchronize); `ms_per_step` is the MEDIAN "
-                        "group, all groups are in the JSON line (benchmarks/common.py:45-60 of the reference: median + IQR over blocks)")
+                   help="with --full: timed groups of --steps steps each (every group bracketed by barrier + synchronize), reported as "
+                        "their median, IQR and every group (benchmarks/common.py:45-60 of the reference: median + IQR over blocks)")
     p.add_argument("--input-sets", type=int, default=3,
                    help="distinct (x, M, grad_out) sets rotated through the timed loop: a training loop feeds a new batch every step, so "
                         "nothing of step k's inputs may be found in the 256 MB Infinity Cache by step k+1 (1 = one set, reported beside it)")
@@ -609,6 +622,25 @@ def cpu_baseline(size, channels, cpu_batch):
     }
 
 
+DUMP_ARRAY_BYTES = 16 << 20  # per array: y and grad_x of the flagship step are 805 MB each; three arrays stay under 64 MB in all
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array as out_dir/<name>.npy in float32.  An array above DUMP_ARRAY_BYTES is stored as a sample of its flattened
+    elements: sorted indices drawn from a generator seeded with the element count, so every run and every build of the same
+    arguments picks the same elements."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        keep = DUMP_ARRAY_BYTES // 4
+        if t.numel() > keep:
+            idx = torch.randint(0, t.numel(), (keep,), generator=torch.Generator().manual_seed(t.numel())).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+
+
 def main():
     args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -674,13 +706,18 @@ def main():
 
     def timed_group(fixed_set=None):
         """EXACTLY --steps steps between barrier + synchronize on both sides; max over ranks.  A HIP event after every step (recorded,
-        never waited for inside the group) gives the longest single step of the group: a stall shows up as one long step."""
+        never waited for inside the group) gives the longest single step of the group: a stall shows up as one long step.  Returns
+        (ms per step, longest step, output of the last step); no earlier output is held across steps."""
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         barrier()
         t0 = time.perf_counter()
         evs[0].record()
+        last = None
         for i in range(args.steps):
-            step(fixed_set)
+            if i + 1 < args.steps:
+                step(fixed_set)
+            else:
+                last = step(fixed_set)
             evs[i + 1].record()
         torch.cuda.synchronize()
         barrier()
@@ -690,13 +727,13 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         per_step = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
-        return dt / args.steps * 1e3, max(per_step)
+        return dt / args.steps * 1e3, max(per_step), last
 
     # A freshly provisioned box starts with cold clocks / lazily paged-in libraries and memory, and the first touch of every large
     # allocation is paid inside whatever loop makes it (round 3's driver run: one 20-step sample 67 % above the same process's other
     # loops).  Settle, untimed and bounded: groups of 10 steps until THREE consecutive groups agree within 2 % and at least 3 s have
     # passed (at most 15 s).  The timed groups below keep exactly the allocation pattern of these loops (no output is held across steps).
-    clocks_before = device_clocks(dev_index)
+    clocks_before = device_clocks(dev_index) if args.full else None
     t_settle = time.perf_counter()
     settle_groups = []
     agree = 0
@@ -716,30 +753,53 @@ def main():
     settle = {"groups_of_10_steps": len(settle_groups), "first_ms_per_step": round(settle_groups[0], 4), "last_ms_per_step": round(settle_groups[-1], 4),
               "slowest_ms_per_step": round(max(settle_groups), 4), "elapsed_s": round(time.perf_counter() - t_settle, 2),
               "rule": ">= 3 consecutive groups within 2 % and >= 3 s (cap 15 s)"}
+    counter[0] = 0  # the settle ran a varying number of steps: from here on the input set of every step depends on the arguments only
+
+    # ---- the headline: --warmup steps, then ONE group of EXACTLY --steps steps (rotated inputs); ms_per_step = its wall time / --steps ----
     for _ in range(args.warmup):
         step()
-    # ---- the timed region: G groups of EXACTLY --steps steps, rotated-input groups (A) interleaved with one-input-set groups (B) ----
-    n_groups = max(1, args.groups)
-    rot, one = [], []
-    for gi in range(n_groups):
-        rot.append(timed_group(None))
-        if n_sets > 1:
-            one.append(timed_group(0))
-    clocks_after = device_clocks(dev_index)
+    ms_per_step, longest_step_ms, y = timed_group(None)
+    y = y.detach()
+    xl, Ml, _ = sets[(counter[0] - 1) % n_sets]  # the input set of the last timed step: its .grad is what that step returned
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": y, "grad_x": xl.grad, "grad_M": Ml.grad})
 
-    def stats(groups):
-        v = sorted(g[0] for g in groups)
-        n = len(v)
-        med = v[n // 2] if n % 2 else 0.5 * (v[n // 2 - 1] + v[n // 2])
-        q = lambda f: v[min(n - 1, max(0, int(round(f * (n - 1)))))]
-        return {"median": round(med, 4), "min": round(v[0], 4), "max": round(v[-1], 4), "iqr": round(q(0.75) - q(0.25), 4),
-                "groups": [round(g[0], 4) for g in groups], "longest_single_step_ms": [round(g[1], 3) for g in groups]}
+    full = None
+    if args.full:
+        # G groups of EXACTLY --steps steps, rotated-input groups (A) interleaved with one-input-set groups (B)
+        n_groups = max(1, args.groups)
+        rot, one = [], []
+        for gi in range(n_groups):
+            rot.append(timed_group(None)[:2])
+            if n_sets > 1:
+                one.append(timed_group(0)[:2])
+        clocks_after = device_clocks(dev_index)
 
-    rot_stats = stats(rot)
-    one_stats = stats(one) if one else None
-    ms_per_step = rot_stats["median"]
-    single_ms = one_stats["median"] if one_stats else None
-    y = step().detach()
+        def stats(groups):
+            v = sorted(g[0] for g in groups)
+            n = len(v)
+            med = v[n // 2] if n % 2 else 0.5 * (v[n // 2 - 1] + v[n // 2])
+            q = lambda f: v[min(n - 1, max(0, int(round(f * (n - 1)))))]
+            return {"median": round(med, 4), "min": round(v[0], 4), "max": round(v[-1], 4), "iqr": round(q(0.75) - q(0.25), 4),
+                    "groups": [round(g[0], 4) for g in groups], "longest_single_step_ms": [round(g[1], 3) for g in groups]}
+
+        rot_stats = stats(rot)
+        one_stats = stats(one) if one else None
+        single_ms = one_stats["median"] if one_stats else None
+        full = {
+            "ms_per_step_median_of_groups": rot_stats["median"],
+            "groups_timing": f"median of {n_groups} groups of {args.steps} steps after the headline, every group bracketed by "
+                             "barrier + synchronize (max over ranks); rotated-input groups interleaved with one-input-set groups",
+            "ms_per_step_groups": rot_stats["groups"],
+            "ms_per_step_min": rot_stats["min"],
+            "ms_per_step_max": rot_stats["max"],
+            "ms_per_step_iqr": rot_stats["iqr"],
+            "longest_single_step_ms_per_group": rot_stats["longest_single_step_ms"],
+            "ms_per_step_one_input_set": round(single_ms, 4) if single_ms is not None else None,
+            "one_input_set": one_stats,
+            "settle": settle,
+            "clocks": {"before": clocks_before, "after": clocks_after},
+        }
 
     # ---- optional: the reassembly of the (global_batch, C, S, S) output on every rank, timed on its own ----
     gather = None
@@ -782,58 +842,6 @@ def main():
     value = global_batch * S * S / (ms_per_step * 1e-3) / 1e6
 
     if rank == 0:
-        with torch.no_grad():
-            kstats, ops = kernel_roofline(sets, S, max(6, min(args.steps, 21)))
-        dom_op = max(ops, key=lambda k: ops[k]["ms"])
-        dom_kernel = max(kstats, key=lambda k: kstats[k]["ms"])
-        # HBM traffic of the dominant op: rocprofv3 PMC cannot run inside this process, so the figure is the committed measurement of this
-        # very command / config (profiles/r0N_pmc_traffic.json: FETCH_SIZE x2 + WRITE_SIZE, separate passes) - quoted only while the
-        # kernel sources of the tree hash to what that measurement recorded (csrc_sha256)
-        traffic = None
-        traffic_note = None
-        pmc_doc = json.load(open(PMC_FILE)) if PMC_FILE else {}
-        src_now = csrc_sha256()
-        if PMC_FILE and pmc_doc.get("csrc_sha256") != src_now:
-            # the counters were collected on other kernel sources than the tree's: not this build's traffic
-            traffic_note = f"not quoted: profiles/{os.path.basename(PMC_FILE)} was measured on kernel sources {str(pmc_doc.get('csrc_sha256'))[:12]}, the tree is {src_now[:12]}"
-        elif (B, C, S) == (256, 3, 512) and PMC_FILE:
-            pmc = pmc_doc.get("kernels", {})
-            fused = "one read" in ops["km_warp2d_bwd"].get("form", "")
-            want = {"km_warp2d_bwd": ("km_warp_bwd_fused_kernel",) if fused else ("km_warp_bwd_tiled_kernel", "km_warp_gm_kernel"), "km_warp2d_fwd": ("km_warp_fwd_box_kernel",),
-                    "km_filter2d_sep_fwd": ("km_blur_reg_kernel<float, 5, false",), "km_filter2d_sep_bwd_input": ("km_blur_reg_kernel<float, 5, true",)}[dom_op]
-            tot = 0
-            for frag in want:
-                hit = [rec["hbm_bytes_per_launch"] for kname, rec in pmc.items() if frag in kname]
-                tot = tot + hit[0] if hit and tot is not None else None
-            traffic = tot
-        roofline = {
-            "bound": "hbm",
-            "kernel": {"km_warp2d_bwd": "km_warp2d_bwd (" + ops["km_warp2d_bwd"].get("form", "") + "; dominant launch: " + dom_kernel + ")"}.get(dom_op, dom_op),
-            "achieved": ops[dom_op]["GBps"],
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": ops[dom_op]["frac_of_hbm_peak"],
-            "traffic": traffic,
-            "traffic_source": (f"profiles/{os.path.basename(PMC_FILE)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, same command; kernel sources {src_now[:12]})"
-                               if traffic else traffic_note),
-            "op_ms": ops[dom_op]["ms"],
-            "alg_bytes_per_call": ops[dom_op]["alg_bytes"],
-            "accounting": "SURVEY.md 8(d): warp fwd 2e, blur fwd 2e, blur bwd 2e, warp bwd 3e bytes per element; op = every launch of the public entry point",
-            "dominant_launch": {"name": dom_kernel, **kstats[dom_kernel], "frac_of_hbm_peak": round(kstats[dom_kernel]["GBps"] / HBM_PEAK_GBS, 4)},
-        }
-        alg_step_bytes = 36 * B * C * S * S
-        # the copy bandwidth of THIS box, measured in this process (round 5 printed the literal 6200.0 of round 2's microbenchmark here)
-        try:
-            copy = measured_streaming_copy(dev)
-            best = max(copy["plain"]["GBps_median"], copy["nontemporal"]["GBps_median"])
-            roofline["measured_streaming_copy_GBps"] = best
-            roofline["measured_streaming_copy"] = copy
-            roofline["frac_of_measured_copy"] = round(ops[dom_op]["GBps"] / best, 4)
-            step_frac_copy = round(alg_step_bytes / (ms_per_step * 1e-3) / 1e9 / best, 4)
-        except Exception as e:  # (informational: never costs the headline)
-            roofline["measured_streaming_copy_GBps"] = None
-            roofline["measured_streaming_copy"] = {"error": f"{type(e).__name__}: {e}"}
-            step_frac_copy = None
         result = {
             "metric": "Mpix/s fwd+bwd warp_perspective+GaussianBlur2d Bx3x512x512",
             "value": round(value, 1),
@@ -852,37 +860,85 @@ def main():
                 "global_batch": global_batch,
                 "parallelism": f"batch-shard x{world} ({args.scaling} scaling), no data-path collective",
             },
-            "timing": f"median of {n_groups} groups of {args.steps} steps, every group bracketed by barrier + synchronize (max over ranks); "
-                      "rotated-input groups interleaved with one-input-set groups",
-            "ms_per_step_groups": rot_stats["groups"],
-            "ms_per_step_min": rot_stats["min"],
-            "ms_per_step_max": rot_stats["max"],
-            "ms_per_step_iqr": rot_stats["iqr"],
-            "longest_single_step_ms_per_group": rot_stats["longest_single_step_ms"],
+            "timing": f"one group of exactly {args.steps} steps after the settle and {args.warmup} warm-up steps, bracketed by barrier + synchronize "
+                      "(max over ranks)",
+            "longest_single_step_ms": round(longest_step_ms, 3),
             "inputs": f"{n_sets} distinct (x, M, grad_out) sets rotated through the timed loop (a new batch every step)",
-            "ms_per_step_one_input_set": round(single_ms, 4) if single_ms is not None else None,
-            "one_input_set": one_stats,
-            "settle": settle,
-            "clocks": {"before": clocks_before, "after": clocks_after},
-            "step_GBps_algorithmic": round(alg_step_bytes / (ms_per_step * 1e-3) / 1e9, 1),
-            "step_frac_of_hbm_peak": round(alg_step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            "step_frac_of_measured_copy": step_frac_copy,
-            "roofline": roofline,
-            "ops": ops,
-            "kernels": kstats,
         }
         if gather is not None:
             result["gather"] = gather
-        if world == 1 and not args.no_extras:
+        if full is not None:
+            with torch.no_grad():
+                kstats, ops = kernel_roofline(sets, S, max(6, min(args.steps, 21)))
+            dom_op = max(ops, key=lambda k: ops[k]["ms"])
+            dom_kernel = max(kstats, key=lambda k: kstats[k]["ms"])
+            # HBM traffic of the dominant op: rocprofv3 PMC cannot run inside this process, so the figure is the committed measurement of this
+            # very command / config (profiles/r0N_pmc_traffic.json: FETCH_SIZE x2 + WRITE_SIZE, separate passes) - quoted only while the
+            # kernel sources of the tree hash to what that measurement recorded (csrc_sha256)
+            traffic = None
+            traffic_note = None
+            pmc_doc = json.load(open(PMC_FILE)) if PMC_FILE else {}
+            src_now = csrc_sha256()
+            if PMC_FILE and pmc_doc.get("csrc_sha256") != src_now:
+                # the counters were collected on other kernel sources than the tree's: not this build's traffic
+                traffic_note = f"not quoted: profiles/{os.path.basename(PMC_FILE)} was measured on kernel sources {str(pmc_doc.get('csrc_sha256'))[:12]}, the tree is {src_now[:12]}"
+            elif (B, C, S) == (256, 3, 512) and PMC_FILE:
+                pmc = pmc_doc.get("kernels", {})
+                fused = "one read" in ops["km_warp2d_bwd"].get("form", "")
+                want = {"km_warp2d_bwd": ("km_warp_bwd_fused_kernel",) if fused else ("km_warp_bwd_tiled_kernel", "km_warp_gm_kernel"), "km_warp2d_fwd": ("km_warp_fwd_box_kernel",),
+                        "km_filter2d_sep_fwd": ("km_blur_reg_kernel<float, 5, false",), "km_filter2d_sep_bwd_input": ("km_blur_reg_kernel<float, 5, true",)}[dom_op]
+                tot = 0
+                for frag in want:
+                    hit = [rec["hbm_bytes_per_launch"] for kname, rec in pmc.items() if frag in kname]
+                    tot = tot + hit[0] if hit and tot is not None else None
+                traffic = tot
+            roofline = {
+                "bound": "hbm",
+                "kernel": {"km_warp2d_bwd": "km_warp2d_bwd (" + ops["km_warp2d_bwd"].get("form", "") + "; dominant launch: " + dom_kernel + ")"}.get(dom_op, dom_op),
+                "achieved": ops[dom_op]["GBps"],
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": ops[dom_op]["frac_of_hbm_peak"],
+                "traffic": traffic,
+                "traffic_source": (f"profiles/{os.path.basename(PMC_FILE)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, same command; kernel sources {src_now[:12]})"
+                                   if traffic else traffic_note),
+                "op_ms": ops[dom_op]["ms"],
+                "alg_bytes_per_call": ops[dom_op]["alg_bytes"],
+                "accounting": "SURVEY.md 8(d): warp fwd 2e, blur fwd 2e, blur bwd 2e, warp bwd 3e bytes per element; op = every launch of the public entry point",
+                "dominant_launch": {"name": dom_kernel, **kstats[dom_kernel], "frac_of_hbm_peak": round(kstats[dom_kernel]["GBps"] / HBM_PEAK_GBS, 4)},
+            }
+            alg_step_bytes = 36 * B * C * S * S
+            # the copy bandwidth of THIS box, measured in this process (round 5 printed the literal 6200.0 of round 2's microbenchmark here)
             try:
-                result["generic_gpu"] = generic_gpu_baseline(dev, S, C)
-            except Exception as e:  # informational only
-                result["generic_gpu"] = {"error": f"{type(e).__name__}: {e}"}
-            result["other_configs"] = other_configs(x.device)
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(S, C, args.cpu_batch)
-        else:
-            result["cpu_baseline"] = None
+                copy = measured_streaming_copy(dev)
+                best = max(copy["plain"]["GBps_median"], copy["nontemporal"]["GBps_median"])
+                roofline["measured_streaming_copy_GBps"] = best
+                roofline["measured_streaming_copy"] = copy
+                roofline["frac_of_measured_copy"] = round(ops[dom_op]["GBps"] / best, 4)
+                step_frac_copy = round(alg_step_bytes / (ms_per_step * 1e-3) / 1e9 / best, 4)
+            except Exception as e:  # (informational: never costs the headline)
+                roofline["measured_streaming_copy_GBps"] = None
+                roofline["measured_streaming_copy"] = {"error": f"{type(e).__name__}: {e}"}
+                step_frac_copy = None
+            result.update(full)
+            result.update({
+                "step_GBps_algorithmic": round(alg_step_bytes / (ms_per_step * 1e-3) / 1e9, 1),
+                "step_frac_of_hbm_peak": round(alg_step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                "step_frac_of_measured_copy": step_frac_copy,
+                "roofline": roofline,
+                "ops": ops,
+                "kernels": kstats,
+            })
+            if world == 1 and not args.no_extras:
+                try:
+                    result["generic_gpu"] = generic_gpu_baseline(dev, S, C)
+                except Exception as e:  # informational only
+                    result["generic_gpu"] = {"error": f"{type(e).__name__}: {e}"}
+                result["other_configs"] = other_configs(x.device)
+            if world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline(S, C, args.cpu_batch)
+            else:
+                result["cpu_baseline"] = None
         print(json.dumps(result), flush=True)
 
     if dist is not None:

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out
 out=gpurun_out/ab_extras.txt
 : > $out
-run() { python bench.py --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+run() { python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('step', d['ms_per_step'], {k:v['ms'] for k,v in d['kernels'].items()})
 oc=d['other_configs']
 for k,v in oc.items(): print('   ', k, v if not isinstance(v,dict) else {a:b for a,b in v.items() if a!='mfma'})"; }

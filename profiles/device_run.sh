@@ -3,7 +3,7 @@
 #   bash profiles/device_run.sh <round-tag> <run-name> <stage> [<stage> ...]
 # stages
 #   suite          pytest -m gpu + __graft_entry__.smoke()
-#   bench:N        the driver's command verbatim (`python3 bench.py --gpus 1 --steps 20 --warmup 5`) N times, every JSON line kept
+#   bench:N        `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full` N times, every JSON line kept
 #   benchlite:N    the same without cpu baseline / other configs (A/B of libraries: KORNIA_AMD_LIB is honoured)
 #   prof           rocprofv3 --kernel-trace --stats of the bench command, then FETCH_SIZE / WRITE_SIZE in separate --pmc passes
 #   units          unit counters (separate --pmc passes) of the four hot launches + km_points -> <run-name>_units/ (pmc_units_to_json.py)
@@ -28,7 +28,7 @@ for stage in "$@"; do
       ;;
     bench:*|benchlite:*)
       n=${stage#*:}
-      extra=""; [ "${stage%%:*}" = benchlite ] && extra="--no-cpu-baseline --no-extras"
+      extra="--full"; [ "${stage%%:*}" = benchlite ] && extra="--full --no-cpu-baseline --no-extras"
       for i in $(seq 1 $n); do
         BENCH_SETTLE_TRACE=1 timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 $extra > $D/.b.out 2> $D/.b.err
         echo "[bench $i rc $?]" >> $O
@@ -42,11 +42,11 @@ for stage in "$@"; do
       P=$D/${RUN}_prof; rm -rf $P; mkdir -p $P
       python3 -c "import bench; print(bench.csrc_sha256())" > $P/csrc.sha256 2>/dev/null
       ( cd /tmp && export TMPDIR=/tmp
-        timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -o f -- python $R/bench.py --no-cpu-baseline --no-extras --steps 10 --warmup 3 --groups 3 > $P/stats.log 2>&1
+        timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -o f -- python $R/bench.py --full --no-cpu-baseline --no-extras --steps 10 --warmup 3 --groups 3 > $P/stats.log 2>&1
         rc=$?; echo "rocprofv3 stats rc $rc" >> $O
         if [ $rc -eq 0 ]; then
           for c in FETCH_SIZE WRITE_SIZE; do
-            timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $P/pmc_$c -o p -- python $R/bench.py --no-cpu-baseline --no-extras --steps 2 --warmup 1 --groups 1 > $P/pmc_$c.log 2>&1
+            timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $P/pmc_$c -o p -- python $R/bench.py --full --no-cpu-baseline --no-extras --steps 2 --warmup 1 --groups 1 > $P/pmc_$c.log 2>&1
             rc=$?; echo "pmc $c rc $rc" >> $O
             [ $rc -ne 0 ] && break
           done

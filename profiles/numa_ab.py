@@ -42,7 +42,7 @@ def parse_cpulist(s):
 def run(label, env_extra, cpus):
     env = dict(os.environ); env.update(env_extra)
     pre = (lambda: os.sched_setaffinity(0, cpus)) if cpus else None
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extras"], env=env, preexec_fn=pre, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-extras"], env=env, preexec_fn=pre, capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     d = json.loads(line[-1]) if line else {}
     r2 = subprocess.run([sys.executable, os.path.abspath(__file__), "--micro"], env=env, preexec_fn=pre, capture_output=True, text=True)

@@ -7,7 +7,7 @@ for i in 1 2; do
     echo "--- library: $l" >> $O
     if [ $l = default ]; then unset KORNIA_AMD_LIB; else export KORNIA_AMD_LIB=$R/kornia_amd/lib/var/lib_$l.so; fi
     timeout 300 python profiles/time_bwd_fused.py >> $O 2>&1
-    timeout 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | grep "^{" | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('step', d['ms_per_step'], d['ms_per_step_groups'], {k: v['ms'] for k, v in d['ops'].items()})" >> $O 2>&1
+    timeout 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras 2>/dev/null | grep "^{" | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('step', d['ms_per_step'], d['ms_per_step_groups'], {k: v['ms'] for k, v in d['ops'].items()})" >> $O 2>&1
   done
 done
 unset KORNIA_AMD_LIB
