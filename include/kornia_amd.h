@@ -28,6 +28,10 @@
  *            version still read 2: a version-2 library may lack them), km_stream_copy; and the sampler follows ATen's CPU rule for
  *            NaN / inf sampling coordinates (taps outside the image are zeros that are still multiplied: NaN out, NaN matrix gradient)
  *            where sets 1-2 returned the padding value.
+ *   Entry points added after set 3 do not move the version (bindings written against set 3 pin it): each group of them is announced by a
+ *   bit of `km_abi_features()`.  That symbol is itself new, so a binding looks it up with dlsym and treats its absence as 0.
+ *     bit 0  km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd (masks, RandomPerspective and inverse() of the
+ *            augmentation container).
  */
 #ifndef KORNIA_AMD_H
 #define KORNIA_AMD_H
@@ -46,6 +50,8 @@ enum { KM_ZEROS = 0, KM_BORDER = 1, KM_REFLECTION = 2, KM_FILL = 3 };
 enum { KM_CONSTANT = 0, KM_REFLECT = 1, KM_REPLICATE = 2, KM_CIRCULAR = 3 };
 
 int km_abi_version(void);
+/* bit mask of the entry-point groups added after set 3 (see Versioning) */
+int km_abi_features(void);
 const char* km_last_error(void);
 /* gcnArchName of the current device into name[n]; returns the CU count or < 0 */
 int km_device_info(char* name, int n);
@@ -56,7 +62,7 @@ int km_device_info(char* name, int n);
 int km_set_traversal(int mode);
 /* Launch policy.  The library reads its A/B switches (profiles/README.md: KM_WARP_FWD_ALGO, KM_BLUR_ROWS, ...) from the environment ONCE,
  * when it is first used; no launcher calls getenv.  km_config_set changes one entry explicitly ("traversal_fixed", "warp_fwd_algo",
- * "warp_gm_algo", "warp_bwd_generic", "warp_bwd_fused", "sep_lds", "sg_generic", "pyrdown_separable", "blur_rows", "warp_bwd_no_scan") and returns its
+ * "warp_gm_algo", "warp_bwd_generic", "warp_bwd_fused", "sep_lds", "sg_generic", "pyrdown_separable", "blur_rows", "warp_bwd_no_scan", "pair_fused") and returns its
  * previous value (-1: unknown key).  For tests and A/B timing - call it between launches, not concurrently with them.  The alternating
  * traversal itself keeps its parity per (device, stream): what one stream launches never changes the order another stream's kernels
  * walk the batch.  (No reference counterpart.) */
@@ -150,6 +156,33 @@ int km_affine_matrix2d_fwd(const void* translations, const void* center, const v
 int km_affine_params_chain_fwd(const void* translations, const void* center, const void* scale, const void* angle, const void* shear_x,
                                const void* shear_y, const void* batch_prob, void* M_out, void* m_out, void* apply, int B, int Hs, int Ws, int hd,
                                int wd, void* stream);
+
+/* [features bit 0] RandomPerspective.compute_transformation (kornia/augmentation/_2d/geometric/perspective.py:92-95 -> get_perspective_transform,
+ * the Heckbert closed form of km_perspective_transform_fwd) + the normalise / invert chain of warp_perspective (imgwarp.py:146-153) + the
+ * batch_prob switch, in one launch (float32).  start_points / end_points (B,4,2) -> M_out (B,9) pixel homography (nullable), m_out (B,9) the
+ * normalised dst->src matrix km_warp2d_fwd reads with coord_mode = perspective; batch_prob (B) or NULL -> apply (B) uint8.  Bit-identical
+ * to km_perspective_transform_fwd followed by km_homography_chain_fwd. */
+int km_perspective_params_chain_fwd(const void* start_points, const void* end_points, const void* batch_prob, void* M_out, void* m_out,
+                                    void* apply, int B, int Hs, int Ws, int hd, int wd, void* stream);
+/* [features bit 0] The inverse warp of a geometric augmentation (kornia/augmentation/_2d/geometric/base.py:352-378): M (B,3,3) float32 forward
+ * pixel matrix -> Minv by the closed-form 3x3 inverse (kornia/core/utils.py:137-166) -> m_out (B,9), the normalised dst->src matrix of
+ * warp_affine(Minv[:, :2]) (rows = 2) or warp_perspective(Minv) (rows = 3) for an (H,W) image to its own size.  (The reference's module
+ * inverse takes Minv with torch.linalg.inv, kornia/core/utils.py:202-218: the two differ in the last bits.) */
+int km_inverse_chain_fwd(const void* M, int rows, void* m_out, int B, int H, int W, void* stream);
+
+/* [features bit 0] An image and a label mask under one draw (kornia/augmentation/container/augment.py:596-618, _2d/geometric/base.py:87-130):
+ * the image as km_warp2d_fwd_masked (bit-identical), the mask element by element as mask.to(image dtype) -> nearest with the same matrix,
+ * padding, align_corners and fill (rounded to the image dtype) -> .to(mask dtype), every sample taking the dtype round trip; apply (B) uint8 or
+ * NULL as in km_warp2d_fwd_masked.  src / dst (B,C,H,W) in dtype (f32 / bf16 / f16) or both NULL (mask only: dtype still names the image
+ * dtype); mask_src / mask_dst (B,Cm,H,W) in mask_dtype; mat (B,9) float32, coord_mode KM_WARP_AFFINE or KM_WARP_PERSPECTIVE; fill (C),
+ * mask_fill (Cm) float32, read for pad == KM_FILL only.  Image + mask are ONE launch (each pixel's coordinate computed once for both) under
+ * a perspective matrix and TWO under an affine one (the image's own forward, then the mask kernel): what measured faster for each
+ * (km_config_set("pair_fused", 1 / 0 / 2 = that default)); the results do not depend on it.  The mask-only kernel writes one 4-byte word per
+ * lane when the element is narrower than 4 bytes (4 x 1-byte / 2 x 2-byte elements per lane, consecutive lanes on consecutive words). */
+enum { KM_MASK_BOOL = 0, KM_MASK_U8 = 1, KM_MASK_I32 = 2, KM_MASK_I64 = 3, KM_MASK_F32 = 4, KM_MASK_BF16 = 5, KM_MASK_F16 = 6 };
+int km_warp2d_pair_fwd(const void* src, void* dst, const void* mask_src, void* mask_dst, const void* mat, const void* apply, int B, int C, int Cm,
+                       int H, int W, int coord_mode, int interp, int pad, int align, const void* fill, const void* mask_fill, int dtype,
+                       int mask_dtype, void* stream);
 
 /* ColorJitter's sampled factors -> the inputs of km_color_jitter_fwd(_masked) in one launch
  * (kornia/augmentation/_2d/intensity/color_jitter.py:137-148, base.py:380): brightness / contrast / saturation / hue (B) fp32

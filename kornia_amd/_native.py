@@ -71,7 +71,14 @@ _PROTOTYPES = {
     "km_warp2d_blur_supported": [_I] * 10,
     "km_transform_points_fwd": [_P, _P, _P] + [_I] * 4 + [_I, _P],
     "km_transform_points_bwd": [_P, _P, _P, _P, _P] + [_I] * 4 + [_I, _P],
+    # km_abi_features() bit 0 (include/kornia_amd.h, Versioning)
+    "km_warp2d_pair_fwd": [_P] * 6 + [_I] * 9 + [_P, _P, _I, _I, _P],
+    "km_perspective_params_chain_fwd": [_P] * 6 + [_I] * 5 + [_P],
+    "km_inverse_chain_fwd": [_P, _I, _P, _I, _I, _I, _P],
 }
+ABI_FEATURES = 1  # the km_abi_features() bits this binding calls
+_FEATURE_SYMBOLS = {"km_warp2d_pair_fwd": 1, "km_perspective_params_chain_fwd": 1, "km_inverse_chain_fwd": 1}
+KM_MASK_CODES = {torch.bool: 0, torch.uint8: 1, torch.int32: 2, torch.int64: 3, torch.float32: 4, torch.bfloat16: 5, torch.float16: 6}
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -103,6 +110,12 @@ def lib() -> ctypes.CDLL:
     got = handle.km_abi_version()
     if got != ABI_VERSION:
         raise NativeLibraryError(f"{LIB_PATH} has ABI version {got}, expected {ABI_VERSION}; rebuild it")
+    feat = getattr(handle, "km_abi_features", None)  # (new after set 3: absent means 0)
+    if feat is not None:
+        feat.restype = c_int
+    have = feat() if feat is not None else 0
+    if have & ABI_FEATURES != ABI_FEATURES:
+        raise NativeLibraryError(f"{LIB_PATH} announces ABI features {have:#x}, expected {ABI_FEATURES:#x}; rebuild it")
     for name, argtypes in _PROTOTYPES.items():
         fn = getattr(handle, name, None)
         if fn is None:
@@ -122,13 +135,26 @@ def lib() -> ctypes.CDLL:
 
 
 def exported_symbols() -> list[str]:
-    return ["km_abi_version", "km_last_error", "km_device_info", "km_set_traversal", "km_config_set", "km_config_get", *_PROTOTYPES.keys()]
+    return ["km_abi_version", "km_abi_features", "km_last_error", "km_device_info", "km_set_traversal", "km_config_set", "km_config_get", *_PROTOTYPES.keys()]
 
 
 def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = lib().km_last_error().decode("utf-8", "replace")
         raise NativeLibraryError(f"{what} failed (rc={rc}): {msg}")
+
+
+def abi_features() -> int:
+    """``km_abi_features()`` of the loaded library (0 when it predates the symbol)."""
+    fn = getattr(lib(), "km_abi_features", None)
+    return int(fn()) if fn is not None else 0
+
+
+def mask_dtype_code(dtype: torch.dtype) -> int:
+    try:
+        return KM_MASK_CODES[dtype]
+    except KeyError:
+        raise TypeError(f"masks may be bool / uint8 / int32 / int64 / float32 / bfloat16 / float16, got {dtype}") from None
 
 
 def dtype_code(dtype: torch.dtype) -> int:

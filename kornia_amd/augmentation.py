@@ -35,8 +35,9 @@ from .filters.gaussian import gaussian_blur2d
 from .geometry.transform.builders import get_affine_matrix2d, get_perspective_transform
 from .geometry.transform.imgwarp import COORD_PERSPECTIVE, _warp, _warp_affine_from_chain, warp_affine, warp_perspective
 
-__all__ = ["AugmentationSequential", "ColorJitter", "ParamItem", "RandomAffine", "RandomGaussianBlur", "affine_chain", "affine_matrix", "apply_sequence",
-           "color_jitter", "gaussian_taps", "random_affine", "random_gaussian_blur", "random_perspective", "select_samples"]
+__all__ = ["AugmentationSequential", "ColorJitter", "ParamItem", "RandomAffine", "RandomGaussianBlur", "RandomPerspective", "affine_chain", "affine_matrix",
+           "apply_sequence", "color_jitter", "gaussian_taps", "inverse_chain", "perspective_chain", "random_affine", "random_gaussian_blur",
+           "random_perspective", "select_samples", "warp_pair"]
 
 
 def _p(params: Mapping[str, Any], key: str, device) -> torch.Tensor:
@@ -177,6 +178,84 @@ def random_perspective(input: torch.Tensor, params: Mapping[str, Any], resample:
     return select_samples(warp_perspective(input, M, size, resample, "zeros", align_corners), input, mask)
 
 
+def perspective_chain(params: Mapping[str, Any], device, height: int, width: int, with_matrix: bool = False):
+    """RandomPerspective's sampled corners -> ``(m, M, apply)`` in ONE launch (``km_perspective_params_chain_fwd`` = get_perspective_transform +
+    warp_perspective's normalise / invert chain + the ``batch_prob > 0.5`` switch), as :func:`affine_chain` does for RandomAffine: m (B,9) float32
+    for a same-size warp of a (height, width) image, M (B,3,3) the pixel homography when ``with_matrix``, apply (B) uint8 or None."""
+    device = torch.device(device)
+    sp, ep = (_p(params, k, device).contiguous() for k in ("start_points", "end_points"))
+    B = sp.shape[0]
+    if sp.shape != (B, 4, 2) or ep.shape != (B, 4, 2):
+        raise ValueError("start_points / end_points must be (B,4,2)")
+    prob = _prob(params, device, B)
+    m = torch.empty(B, 9, device=device, dtype=torch.float32)
+    M = torch.empty(B, 3, 3, device=device, dtype=torch.float32) if with_matrix else None
+    apply = torch.empty(B, device=device, dtype=torch.uint8) if prob is not None else None
+    with N.device_guard(device):
+        N.check(N.lib().km_perspective_params_chain_fwd(sp.data_ptr(), ep.data_ptr(), N.ptr(prob), N.ptr(M), m.data_ptr(), N.ptr(apply), B, int(height),
+                                                        int(width), int(height), int(width), N.stream_ptr(device)), "km_perspective_params_chain_fwd")
+    return m, M, apply
+
+
+def inverse_chain(M: torch.Tensor, height: int, width: int, affine: bool) -> torch.Tensor:
+    """(B,3,3) forward pixel matrix -> (B,9) float32, the normalised matrix the sampler reads for the INVERSE warp of a (height, width) image
+    (``km_inverse_chain_fwd``: the closed-form 3x3 inverse, then warp_affine's - ``affine`` - or warp_perspective's normalise / invert chain)."""
+    Mc = M.detach().to(torch.float32).reshape(-1, 3, 3).contiguous()
+    B = Mc.shape[0]
+    m = torch.empty(B, 9, device=Mc.device, dtype=torch.float32)
+    with N.device_guard(Mc.device):
+        N.check(N.lib().km_inverse_chain_fwd(Mc.data_ptr(), 2 if affine else 3, m.data_ptr(), B, int(height), int(width), N.stream_ptr(Mc.device)),
+                "km_inverse_chain_fwd")
+    return m
+
+
+def _fill_vector(fill_value, C: int, device) -> torch.Tensor:
+    """A fill value - a number, a one-element tensor or one value per channel - as the (C,) float32 device vector the sampler reads."""
+    f = torch.as_tensor(fill_value if fill_value is not None else 0.0, dtype=torch.float32).detach().to(device=device, dtype=torch.float32).reshape(-1)
+    if f.numel() == 1:
+        return f.expand(C).contiguous()
+    if f.numel() != C:
+        raise ValueError(f"fill_value has {f.numel()} entries for {C} channels")
+    return f.contiguous()
+
+
+def warp_pair(image: Optional[torch.Tensor], mask: torch.Tensor, m: torch.Tensor, affine: bool, resample: str = "bilinear", padding_mode: str = "zeros",
+              align_corners: bool = False, fill_value=None, apply: Optional[torch.Tensor] = None, image_dtype: Optional[torch.dtype] = None):
+    """An image and its label mask under one normalised (B,9) float32 matrix and per-sample switch, in one native call
+    (``km_warp2d_pair_fwd``): the image as :func:`_warp_affine_from_chain` / the masked perspective warp return it (bit-identical), the mask
+    as ``warp(mask.to(image dtype), mode="nearest", ...).to(mask.dtype)`` - the augmentation container's treatment of masks
+    (kornia/augmentation/container/augment.py:596-618).  ``image`` None: the mask alone (``image_dtype`` names the dtype of its round trip).
+    Returns ``(image_out or None, mask_out)``.  Forward only."""
+    from .geometry.transform.imgwarp import _mode_codes, _prepare_fill
+    dt = image.dtype if image is not None else image_dtype
+    if dt not in (torch.float32, torch.bfloat16, torch.float16):
+        raise TypeError(f"the pair warp takes float32 / bfloat16 / float16 images, got {dt}")
+    N.require_device(mask, "mask")
+    B, Cm, H, W = mask.shape
+    dev = mask.device
+    if image is not None and (image.dim() != 4 or image.shape[0] != B or tuple(image.shape[-2:]) != (H, W) or image.device != dev):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match the image {tuple(image.shape)}")
+    if m.dtype != torch.float32 or tuple(m.shape) != (B, 9):
+        raise TypeError("the pair warp takes a (B,9) float32 matrix")
+    interp, pad = _mode_codes(resample, padding_mode)
+    x = image.detach().contiguous() if image is not None else None
+    C = x.shape[1] if x is not None else 0
+    out = torch.empty_like(x) if x is not None else None
+    mk = mask.detach().contiguous()
+    mout = torch.empty_like(mk)
+    fill = mfill = None
+    if padding_mode == "fill":
+        fv = torch.zeros(C or 1) if fill_value is None else fill_value
+        fill = _prepare_fill(fv if isinstance(fv, torch.Tensor) else torch.full((C,), float(fv)), C, dev, torch.float32) if C else None
+        mfill = _fill_vector(fv, Cm, dev)  # (one value, or one per mask channel: a per-colour fill has no meaning for a label mask)
+    flags = N.flags(apply, dev, B) if apply is not None else None
+    with N.device_guard(dev):
+        N.check(N.lib().km_warp2d_pair_fwd(N.ptr(x), N.ptr(out), mk.data_ptr(), mout.data_ptr(), m.data_ptr(), N.ptr(flags), B, C, Cm, H, W,
+                                           1 if affine else 0, interp, pad, int(bool(align_corners)), N.ptr(fill), N.ptr(mfill), N.dtype_code(dt),
+                                           N.mask_dtype_code(mk.dtype), N.stream_ptr(dev)), "km_warp2d_pair_fwd")
+    return out, mout
+
+
 def color_jitter(input: torch.Tensor, params: Mapping[str, Any], order: Optional[Sequence[int]] = None) -> torch.Tensor:
     """ColorJitter.apply_transform (color_jitter.py:126-159): brightness / contrast / saturation / hue in ``params['order']``
     (or the module's fixed ``order``), each stage skipped when its factors are all neutral."""
@@ -250,7 +329,8 @@ def apply_sequence(input: torch.Tensor, affine: Mapping[str, Any], jitter: Mappi
 #   * a module's draws land in ONE host buffer and cross to the device as ONE copy (the reference moves every parameter tensor on its own);
 #     ``_params`` exposes host views with the reference's keys, so a replay through Kornia - or of Kornia's through this - works;
 #   * the apply step is the functions above: the per-sample probability switch inside the launches, no blend pass, no host synchronisation.
-# Only what config 3 spells: 4-D (or 3-D) image tensors, ``data_keys=["input"]``, no ``random_apply``; everything else raises.
+# Round 7 adds RandomPerspective, label masks in the container (``data_keys`` with "mask" entries) and ``inverse()``; keypoints, boxes,
+# dictionaries, lists of masks and ``random_apply`` still raise.
 from collections import namedtuple
 
 ParamItem = namedtuple("ParamItem", ["name", "data"])  # (module name, parameter dictionary): what ``AugmentationSequential._params`` holds
@@ -342,6 +422,8 @@ class _RandomOp(torch.nn.Module):
     def _apply(self, x: torch.Tensor, params: dict) -> torch.Tensor:
         raise NotImplementedError
 
+    _GEOMETRIC = False  # a geometric module warps masks with its draw; the others leave them alone
+
     def _batch_prob(self, B: int, out: torch.Tensor) -> torch.Tensor:
         # base.py:179-215: a batch-level gate (p_batch) first, then the per-sample gates; certain outcomes consume nothing
         gate = 1.0
@@ -428,11 +510,90 @@ class _RandomOp(torch.nn.Module):
         elif not _own:
             self._st["host_buf"] = None
         self._st["params"] = dict(params)
+        self._st["device"] = x.device
         out = self._apply(x, self._device_params(self._st["params"], x.device, own))
         return out[0] if (input.dim() == 3 and self.keepdim) else out
 
 
-class RandomAffine(_RandomOp):
+class _GeometricOp(_RandomOp):
+    """What RandomAffine and RandomPerspective share beyond the draws: the parameters -> (m, M, apply) chain, label masks warped with the
+    image's draw (``km_warp2d_pair_fwd``), the inverse warp (``km_inverse_chain_fwd`` + the same pair launch) and ``transform_matrix``."""
+
+    _GEOMETRIC = True
+    _AFFINE = True  # the warp's coordinate generator: affine or perspective
+
+    def _chain(self, params: Mapping[str, Any], device, H: int, W: int, with_matrix: bool = False):
+        raise NotImplementedError
+
+    def _fill(self):
+        return self.fill_value
+
+    def _warp_with_masks(self, x: torch.Tensor, masks: list, m: torch.Tensor, apply, image_dtype: torch.dtype, image=True):
+        """The image (unless ``image`` is False: it was warped elsewhere) + the first mask in one pair launch, further masks mask-only on the
+        same matrix and switch."""
+        kw = dict(affine=self._AFFINE, resample=self.resample, padding_mode=self.padding_mode, align_corners=self.align_corners,
+                  fill_value=self._fill(), apply=apply, image_dtype=image_dtype)
+        out, res = x, []
+        for k, mk in enumerate(masks):
+            o, mo = warp_pair(x if (image and k == 0) else None, mk, m, **kw)
+            if image and k == 0:
+                out = o
+            res.append(mo)
+        if image and not masks:
+            out, _ = warp_pair(x, x.new_empty((x.shape[0], 0, x.shape[2], x.shape[3]), dtype=torch.uint8), m, **kw)
+        return out, res
+
+    def _forward_masks(self, x: torch.Tensor, masks: list, params: Mapping[str, Any], own: bool, image_dtype: torch.dtype):
+        """One call of the container with masks: x (B,C,H,W) and masks (B,Cm,H,W) -> (x', masks')."""
+        if not own:
+            self._st["host_buf"] = None
+        self._st["params"] = dict(params)
+        self._st["device"] = x.device
+        p = self._device_params(self._st["params"], x.device, own)
+        B, _, H, W = x.shape
+        m, _, apply = self._chain(p, x.device, H, W)
+        if torch.is_grad_enabled() and x.requires_grad:  # the image through the differentiable composition, the masks on the chain's matrix
+            return self._apply(x, p), self._warp_with_masks(x, masks, m, apply, image_dtype, image=False)[1]
+        return self._warp_with_masks(x, masks, m, apply, image_dtype)
+
+    def _inverse_masks(self, x: torch.Tensor, masks: list, params: Mapping[str, Any], image_dtype: torch.dtype):
+        """The inverse warp of this module's draw (kornia/augmentation/_2d/geometric/base.py:352-378): Minv by the closed form, samples whose
+        draw failed copied, masks nearest."""
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("inverse() is forward-only here (no autograd through the inverse warp)")
+        p = self._device_params(dict(params), x.device, False)
+        B, _, H, W = x.shape
+        _, M, apply = self._chain(p, x.device, H, W, with_matrix=True)
+        return self._warp_with_masks(x, masks, inverse_chain(M, H, W, self._AFFINE), apply, image_dtype)
+
+    def inverse(self, input: torch.Tensor, params: Optional[Mapping[str, Any]] = None, **kwargs) -> torch.Tensor:
+        """``kornia.augmentation``'s module inverse (kornia/augmentation/_2d/geometric/base.py:352-378) for an image: the inverse warp of the
+        last call's draw (or of ``params``), samples whose probability draw failed returned as they are."""
+        if kwargs:
+            raise NotImplementedError(f"inverse(): keyword overrides {sorted(kwargs)} are not supported here")
+        params = self._params if params is None else params
+        if not params:
+            raise ValueError("No parameters available for inversing, please run a forward pass first or passing valid params into this function.")
+        N.require_device(input, "input")
+        x = input.unsqueeze(0) if input.dim() == 3 else input
+        out, _ = self._inverse_masks(x, [], params, x.dtype)
+        return out[0] if (input.dim() == 3 and self.keepdim) else out
+
+    @property
+    def transform_matrix(self) -> Optional[torch.Tensor]:
+        """(B,3,3) pixel matrix of the last call (identity for the samples whose probability draw failed), computed on demand on the device of
+        the last input."""
+        if not self._params:
+            return None
+        shp = self._params["forward_input_shape"].tolist()
+        dev = self._st.get("device") or torch.device("cuda")
+        _, M, apply = self._chain(self._params, dev, shp[-2], shp[-1], with_matrix=True)
+        if apply is not None:
+            M = torch.where(apply.bool().view(-1, 1, 1), M, torch.eye(3, device=M.device).expand_as(M))
+        return M
+
+
+class RandomAffine(_GeometricOp):
     """``kornia.augmentation.RandomAffine`` (kornia/augmentation/_2d/geometric/affine.py:33-162) on the native path: the same constructor,
     the same parameter draws, parameters -> matrix -> normalise / invert in one launch, the warp with the probability switch inside it."""
 
@@ -532,17 +693,64 @@ class RandomAffine(_RandomOp):
             fill = torch.full((x.shape[1],), float(fill))
         return random_affine(x, params, self.resample, self.align_corners, self.padding_mode, fill)
 
-    @property
-    def transform_matrix(self) -> Optional[torch.Tensor]:
-        """(B,3,3) pixel matrix of the last call (identity for the samples whose probability draw failed), computed on demand."""
-        if not self._params:
-            return None
-        shp = self._params["forward_input_shape"].tolist()
-        dev = "cuda"
-        _, M, apply = affine_chain(self._params, dev, shp[-2], shp[-1], with_matrix=True)
-        if apply is not None:
-            M = torch.where(apply.bool().view(-1, 1, 1), M, torch.eye(3, device=M.device).expand_as(M))
-        return M
+    def _chain(self, params, device, H, W, with_matrix=False):
+        return affine_chain(params, device, H, W, with_matrix)
+
+
+class RandomPerspective(_GeometricOp):
+    """``kornia.augmentation.RandomPerspective`` (kornia/augmentation/_2d/geometric/perspective.py:30-130, random_generator/_2d/perspective.py)
+    on the native path: the same constructor and draws, corners -> homography -> normalise / invert in one launch
+    (``km_perspective_params_chain_fwd``), the warp with the probability switch inside it."""
+
+    _FLOATS_PER_SAMPLE = 17  # batch_prob, start points (8), end points (8)
+    _AFFINE = False
+
+    def __init__(self, distortion_scale=0.5, resample="BILINEAR", same_on_batch: bool = False, align_corners: bool = False, p: float = 0.5,
+                 keepdim: bool = False, sampling_method: str = "basic") -> None:
+        super().__init__(p, same_on_batch, keepdim)
+        if sampling_method not in ("basic", "area_preserving"):
+            raise NotImplementedError(f"Sampling method {sampling_method} not yet implemented.")
+        d = distortion_scale.detach().to(torch.float32).cpu() if isinstance(distortion_scale, torch.Tensor) else torch.as_tensor(distortion_scale, dtype=torch.float32)
+        if not (d.dim() == 0 and 0 <= float(d) <= 1):
+            raise AssertionError(f"'distortion_scale' must be a scalar within [0, 1]. Got {d}.")
+        self.distortion_scale = d
+        self.sampling_method = sampling_method
+        self.resample = str(getattr(resample, "name", resample)).lower()
+        self.align_corners = bool(align_corners)
+        self.padding_mode = "zeros"
+        self.fill_value = None
+
+    def _sample(self, d: _Draws, shape, params: dict) -> None:
+        # random_generator/_2d/perspective.py: the image corners, factor = (d W / 2, d H / 2), ONE draw of (B, 4, 2) uniforms (1 x 4 x 2 with
+        # same_on_batch), offset = factor * rand * corner signs ('basic') or 2 factor (rand - 0.5) ('area_preserving'), all in float32
+        B, H, W = int(shape[0]), int(shape[-2]), int(shape[-1])
+        start, end = d.piece(B, 4, 2), d.piece(B, 4, 2)
+        geo = self._st.get("geo")
+        if geo is None or geo[2] != (H, W):
+            corners = torch.tensor([[[0.0, 0], [W - 1, 0], [W - 1, H - 1], [0, H - 1]]], dtype=torch.float32)
+            factor = torch.stack([self.distortion_scale * W / 2, self.distortion_scale * H / 2], dim=0).view(-1, 1, 2)
+            geo = self._st["geo"] = (corners, factor, (H, W))
+        corners, factor = geo[0], geo[1]
+        rand = torch.rand(1 if self.same_on_batch else B, 4, 2, dtype=torch.float32)
+        if self.same_on_batch:
+            rand = rand.expand(B, 4, 2)
+        if self.sampling_method == "basic":
+            offset = factor * rand * torch.tensor([[[1.0, 1], [-1, 1], [-1, -1], [1, -1]]], dtype=torch.float32)
+        else:
+            offset = 2 * factor * (rand - 0.5)
+        start.copy_(corners.expand(B, 4, 2))
+        torch.add(corners, offset, out=end)
+        params.update(start_points=start, end_points=end)
+
+    def _apply(self, x: torch.Tensor, params: dict) -> torch.Tensor:
+        if x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16, torch.float16) and not (torch.is_grad_enabled() and x.requires_grad):
+            B, C, H, W = x.shape
+            m, _, apply = perspective_chain(params, x.device, H, W)
+            return self._warp_with_masks(x, [], m, apply, x.dtype)[0]
+        return random_perspective(x, params, self.resample, self.align_corners)
+
+    def _chain(self, params, device, H, W, with_matrix=False):
+        return perspective_chain(params, device, H, W, with_matrix)
 
 
 class ColorJitter(_RandomOp):
@@ -608,22 +816,31 @@ class RandomGaussianBlur(_RandomOp):
         return random_gaussian_blur(x, params, self.kernel_size, self.border_type, self.separable)
 
 
+_MASK_REFUSED = ("keypoints, boxes, dictionaries, lists of masks and random_apply are not supported here; use Kornia's container with "
+                 "kornia_amd.patch()")
+
+
 class AugmentationSequential(torch.nn.Module):
-    """``kornia.augmentation.AugmentationSequential`` for image tensors (kornia/augmentation/container/augment.py:431-500): every child samples
-    its parameters and transforms the previous child's output; ``params=`` replays a list of ``ParamItem(name, data)`` (this container's
-    ``_params`` - or Kornia's own: the names and keys are the reference's)."""
+    """``kornia.augmentation.AugmentationSequential`` (kornia/augmentation/container/augment.py:431-500) for one image tensor and any number of
+    label masks: every child samples its parameters and transforms the previous child's output; ``params=`` replays a list of
+    ``ParamItem(name, data)`` (this container's ``_params`` - or Kornia's own: the names and keys are the reference's).
+
+    ``data_keys``: one ``"input"`` (or ``"image"``) and any number of ``"mask"`` entries, in any order; the call takes and returns the tensors in
+    that order.  A mask is (B, Cm, H, W) - (Cm, H, W) with a (C, H, W) image - of dtype bool / uint8 / int32 / int64 / float32 / bfloat16 /
+    float16, and takes the reference's round trip (augment.py:596-618): cast to the image dtype, warped by each geometric child with ``nearest``
+    and that child's padding, ``align_corners`` and fill, cast back to the dtype of the LAST mask of ``data_keys`` (the reference's
+    ``mask_dtype``); intensity children leave masks alone.  The first mask rides in the image's launch, further masks get mask-only launches on
+    the same matrix and switch (``km_warp2d_pair_fwd``).  :meth:`inverse` walks the children backwards."""
 
     def __init__(self, *args: torch.nn.Module, data_keys=("input",), same_on_batch: Optional[bool] = None, keepdim: Optional[bool] = None,
                  random_apply=False, random_apply_weights=None, transformation_matrix_mode: str = "silent", extra_args=None) -> None:
         super().__init__()
-        keys = [str(getattr(k, "name", k)).lower() for k in (data_keys or ("input",))]
-        if keys not in (["input"], ["image"], ["0"]):
-            raise NotImplementedError(f"only image tensors are supported here (data_keys={list(data_keys)}); use Kornia's container with kornia_amd.patch() for masks / boxes / keypoints")
+        keys = self._parse_keys(data_keys)
         if random_apply not in (False, None) or random_apply_weights is not None:
-            raise NotImplementedError("random_apply is not supported here; use Kornia's container with kornia_amd.patch()")
+            raise NotImplementedError(f"random_apply: {_MASK_REFUSED}")
         for i, m in enumerate(args):
             if not isinstance(m, _RandomOp):
-                raise NotImplementedError(f"child {i} ({type(m).__name__}) is not one of this package's modules (RandomAffine, ColorJitter, RandomGaussianBlur)")
+                raise NotImplementedError(f"child {i} ({type(m).__name__}) is not one of this package's modules (RandomAffine, RandomPerspective, ColorJitter, RandomGaussianBlur)")
             if same_on_batch is not None:
                 m.same_on_batch = bool(same_on_batch)
             if keepdim is not None:
@@ -633,6 +850,20 @@ class AugmentationSequential(torch.nn.Module):
         object.__setattr__(self, "_params", [])
         object.__setattr__(self, "_draws", None)
         object.__setattr__(self, "_kids", list(self.named_children()))
+        object.__setattr__(self, "_keys", keys)
+        self._check_masks(keys)
+
+    @staticmethod
+    def _parse_keys(data_keys) -> list:
+        if isinstance(data_keys, dict):
+            raise NotImplementedError(f"data_keys={data_keys!r}: {_MASK_REFUSED}")
+        keys = []
+        for k in (data_keys or ("input",)):
+            k = str(getattr(k, "name", k)).lower()
+            keys.append("input" if k in ("input", "image", "0") else k)
+        if keys.count("input") != 1 or any(k not in ("input", "mask") for k in keys):
+            raise NotImplementedError(f"data_keys={list(data_keys)}: one image key ('input' / 'image') and any number of 'mask' keys are supported; {_MASK_REFUSED}")
+        return keys
 
     def forward_parameters(self, batch_shape) -> list:
         """One ``ParamItem`` per child, sampled in order (a same-size pipeline: every child sees the input's shape); the draws of ALL children
@@ -644,7 +875,9 @@ class AugmentationSequential(torch.nn.Module):
         object.__setattr__(self, "_draws", d)
         return items
 
-    def forward(self, input: torch.Tensor, params: Optional[Sequence[ParamItem]] = None) -> torch.Tensor:
+    def _prepare(self, input: torch.Tensor, params):
+        """This call's parameters and whether the children may take the device copy handed to them (their own draws, or a replay whose float
+        tensors share one host allocation)."""
         children = self._kids
         if params is not None and len(params) != len(children):
             raise ValueError(f"{len(params)} parameter items for {len(children)} children")
@@ -677,9 +910,100 @@ class AugmentationSequential(torch.nn.Module):
                     m._st["host_buf"] = buf
                     m._dev_buf = dev
                 own = True
-        out, used = input, []
-        for i, (name, m) in enumerate(children):
-            out = m(out, params[i].data, _own=own)
-            used.append(ParamItem(name, m._params))
-        object.__setattr__(self, "_params", used)
-        return out
+        return params, own
+
+    def _split(self, args, keys):
+        """(image, [masks], unbatched) from the call's tensors in ``keys`` order, masks checked against the image and made 4-D."""
+        if len(args) != len(keys):
+            raise NotImplementedError(f"{len(args)} inputs for data_keys={keys}; {_MASK_REFUSED}")
+        for a in args:
+            if not isinstance(a, torch.Tensor):
+                raise NotImplementedError(f"inputs must be tensors, got {type(a).__name__}; {_MASK_REFUSED}")
+        img = args[keys.index("input")]
+        N.require_device(img, "input")
+        if img.dim() not in (3, 4):
+            raise ValueError(f"expected a (B, C, H, W) or (C, H, W) image tensor, got {tuple(img.shape)}")
+        x = img.unsqueeze(0) if img.dim() == 3 else img
+        masks = []
+        for a, k in zip(args, keys):
+            if k != "mask":
+                continue
+            N.require_device(a, "mask")
+            mk = a.unsqueeze(0) if (a.dim() == 3 and img.dim() == 3) else a
+            if mk.dim() != 4 or mk.shape[0] != x.shape[0] or mk.shape[-2:] != x.shape[-2:]:
+                raise ValueError(f"a mask must be (B, Cm, H, W) with the image's B, H and W {tuple(x.shape)} (or (Cm, H, W) with a (C, H, W) image), "
+                                 f"got {tuple(a.shape)}")
+            N.mask_dtype_code(mk.dtype)
+            masks.append(mk)
+        return x, masks, img.dim() == 3
+
+    def _run_masks(self, args, keys, walk):
+        x, masks, unbatched = self._split(args, keys)
+        out_dtype = masks[-1].dtype if masks else None  # (the reference's mask_dtype: the last mask's, for every mask)
+        work = [mk if mk.dtype == out_dtype else mk.to(x.dtype) for mk in masks]  # (another dtype: cast once, so that its round trip is the reference's)
+        x, work = walk(x, work, x.dtype)
+        work = [mk if mk.dtype == out_dtype else mk.to(out_dtype) for mk in work]
+        keep = unbatched and any(m.keepdim for _, m in self._kids)
+        outs, it = [], iter(work)
+        for k in keys:
+            t = x if k == "input" else next(it)
+            outs.append(t[0] if keep else t)
+        return outs[0] if len(outs) == 1 else tuple(outs)
+
+    def _check_masks(self, keys) -> None:
+        if "mask" in keys and not any(m._GEOMETRIC for _, m in self._kids):
+            # (a mask pipeline without a geometric child would only cast the masks there and back)
+            raise NotImplementedError("masks go with a geometric child (RandomAffine, RandomPerspective); this pipeline has none")
+
+    def forward(self, *args: torch.Tensor, params: Optional[Sequence[ParamItem]] = None, data_keys=None):
+        keys = self._keys if data_keys is None else self._parse_keys(data_keys)
+        if data_keys is not None:
+            self._check_masks(keys)
+        if len(args) == 2 and keys == ["input"] and (args[1] is None or isinstance(args[1], (list, tuple))):
+            args, params = args[:1], args[1]  # (the image-only signature forward(input, params))
+        children = self._kids
+        if keys == ["input"] and len(args) == 1:
+            input = args[0]
+            params, own = self._prepare(input, params)
+            out, used = input, []
+            for i, (name, m) in enumerate(children):
+                out = m(out, params[i].data, _own=own)
+                used.append(ParamItem(name, m._params))
+            object.__setattr__(self, "_params", used)
+            return out
+        img = args[keys.index("input")] if len(args) == len(keys) else args[0]
+        params, own = self._prepare(img.unsqueeze(0) if img.dim() == 3 else img, params)
+
+        def walk(x, masks, image_dtype):
+            used = []
+            for i, (name, m) in enumerate(children):
+                if m._GEOMETRIC:
+                    x, masks = m._forward_masks(x, masks, params[i].data, own, image_dtype)
+                else:
+                    x = m(x, params[i].data, _own=own)
+                used.append(ParamItem(name, m._params))
+            object.__setattr__(self, "_params", used)
+            return x, masks
+
+        return self._run_masks(args, keys, walk)
+
+    def inverse(self, *args: torch.Tensor, params: Optional[Sequence[ParamItem]] = None, data_keys=None):
+        """The inverse of the last call (or of ``params``) for the image and masks (kornia/augmentation/container/augment.py:300-350): the children
+        in reverse, geometric ones by the inverse warp of their draw (samples whose probability draw failed returned as they are, masks nearest),
+        intensity ones the identity."""
+        keys = self._keys if data_keys is None else self._parse_keys(data_keys)
+        self._check_masks(keys)
+        if params is None:
+            if not self._params:
+                raise ValueError("No parameters available for inversing, please run a forward pass first or passing valid params into this function.")
+            params = self._params
+        if len(params) != len(self._kids):
+            raise ValueError(f"{len(params)} parameter items for {len(self._kids)} children")
+
+        def walk(x, masks, image_dtype):
+            for (name, m), item in reversed(list(zip(self._kids, params))):
+                if m._GEOMETRIC:
+                    x, masks = m._inverse_masks(x, masks, item.data, image_dtype)
+            return x, masks
+
+        return self._run_masks(args, keys, walk)

@@ -287,13 +287,12 @@ __device__ __forceinline__ void km_square_to_quad(const R* q, R (&o)[8]) {
     o[6] = g; o[7] = h;
 }
 
+// the homography of sample b (H[2][2] == 1): what km_perspective_transform_kernel writes and km_perspective_params_chain_kernel chains
 template <typename R>
-__global__ __launch_bounds__(64) void km_perspective_transform_kernel(const R* src, const R* dst, R* out, int B) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= B) return;
+__device__ __forceinline__ void km_perspective_of(const R* src, const R* dst, R (&out)[9]) {
     R s[8], d[8];
-    km_square_to_quad<R>(src + (size_t)b * 8, s);
-    km_square_to_quad<R>(dst + (size_t)b * 8, d);
+    km_square_to_quad<R>(src, s);
+    km_square_to_quad<R>(dst, d);
     const R a = s[0], bb = s[1], c = s[2], dd = s[3], e = s[4], f = s[5], g = s[6], h = s[7];
     // adjugate of [[a,b,c],[d,e,f],[g,h,1]]
     const R j00 = e - f * h, j01 = c * h - bb, j02 = bb * f - c * e;
@@ -304,7 +303,65 @@ __global__ __launch_bounds__(64) void km_perspective_transform_kernel(const R* s
     m[3] = d[3] * j00 + d[4] * j10 + d[5] * j20; m[4] = d[3] * j01 + d[4] * j11 + d[5] * j21; m[5] = d[3] * j02 + d[4] * j12 + d[5] * j22;
     m[6] = d[6] * j00 + d[7] * j10 + j20; m[7] = d[6] * j01 + d[7] * j11 + j21; m[8] = d[6] * j02 + d[7] * j12 + j22;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) out[(size_t)b * 9 + k] = m[k] / m[8];
+    for (int k = 0; k < 9; ++k) out[k] = m[k] / m[8];
+}
+
+template <typename R>
+__global__ __launch_bounds__(64) void km_perspective_transform_kernel(const R* src, const R* dst, R* out, int B) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    R m[9];
+    km_perspective_of<R>(src + (size_t)b * 8, dst + (size_t)b * 8, m);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out[(size_t)b * 9 + k] = m[k];
+}
+
+// m = inv(Nd M inv(Ns)) of km_chain_fwd_kernel for a float32 pixel matrix already in registers (rows == 3: M as it is; the caller sets the
+// last row of an affine matrix to (0, 0, 1) first, as convert_affinematrix_to_homography does)
+__device__ __forceinline__ void km_normalise_invert(const KmChainArgs<float>& ch, const float (&M)[9], float (&mi)[9]) {
+    const float Ns[9] = {ch.sx_s, 0, -1, 0, ch.sy_s, -1, 0, 0, 1};
+    const float Nd[9] = {ch.sx_d, 0, -1, 0, ch.sy_d, -1, 0, 0, 1};
+    float Nsi[9], t[9], A[9];
+    km_inv3(Ns, Nsi);
+    km_mm3(M, Nsi, t);
+    km_mm3(Nd, t, A);
+    km_inv3(A, mi);
+}
+
+// RandomPerspective.compute_transformation (kornia/augmentation/_2d/geometric/perspective.py:92-95 -> get_perspective_transform) + the
+// normalise / invert chain of warp_perspective (imgwarp.py:146-153) + the batch_prob switch (base.py:380) in ONE launch
+__global__ __launch_bounds__(64) void km_perspective_params_chain_kernel(const float* start, const float* end, const float* prob, float* M_out,
+                                                                         const KmChainArgs<float> ch, uint8_t* apply) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= ch.B) return;
+    if (apply) apply[b] = (prob[b] > 0.5f) ? 1 : 0;
+    float M[9], mi[9];
+    km_perspective_of<float>(start + (size_t)b * 8, end + (size_t)b * 8, M);
+    if (M_out) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) M_out[(size_t)b * 9 + k] = M[k];
+    }
+    km_normalise_invert(ch, M, mi);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) ch.m[(size_t)b * 9 + k] = mi[k];
+}
+
+// The inverse warp of a geometric augmentation (kornia/augmentation/_2d/geometric/base.py:352-378 + the module's inverse_transform):
+// Minv = km_inv3(M) - the closed form the warps themselves use (kornia/core/utils.py:137-166) - then warp_affine's (rows == 2: the
+// top two rows of Minv) or warp_perspective's (rows == 3) normalise / invert chain, in one launch.
+__global__ __launch_bounds__(64) void km_inverse_chain_kernel(const float* Mp, const KmChainArgs<float> ch) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= ch.B) return;
+    float M[9], Mi[9], mi[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) M[k] = Mp[(size_t)b * 9 + k];
+    km_inv3(M, Mi);
+    if (ch.rows == 2) {
+        Mi[6] = 0; Mi[7] = 0; Mi[8] = 1;
+    }
+    km_normalise_invert(ch, Mi, mi);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) ch.m[(size_t)b * 9 + k] = mi[k];
 }
 
 extern "C" {
@@ -380,6 +437,37 @@ int km_perspective_transform_fwd(const void* points_src, const void* points_dst,
         hipLaunchKernelGGL(km_perspective_transform_kernel<double>, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const double*)points_src,
                            (const double*)points_dst, (double*)out, B);
     return km_check_launch("km_perspective_transform_fwd");
+}
+
+// RandomPerspective's sampled corners -> what the warp kernel reads, in one launch: start_points / end_points (B,4,2) fp32 -> M_out (B,9) the
+// pixel homography (nullable; bit-identical to km_perspective_transform_fwd) and m_out (B,9) the normalised dst->src matrix of warp_perspective
+// for a (Hs,Ws) source and a (hd,wd) destination (bit-identical to km_homography_chain_fwd of that M); batch_prob (B) fp32 or null -> apply (B) uint8.
+int km_perspective_params_chain_fwd(const void* start_points, const void* end_points, const void* batch_prob, void* M_out, void* m_out, void* apply,
+                                    int B, int Hs, int Ws, int hd, int wd, void* stream) {
+    if (B == 0) return 0;
+    KM_REQUIRE(start_points && end_points && m_out, "km_perspective_params_chain_fwd: null pointer");
+    KM_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && hd > 0 && wd > 0, "km_perspective_params_chain_fwd: bad sizes");
+    KM_REQUIRE((batch_prob == nullptr) == (apply == nullptr), "km_perspective_params_chain_fwd: batch_prob and apply go together");
+    KmChainArgs<float> ch;
+    ch.M = nullptr; ch.A = nullptr; ch.m = (float*)m_out; ch.gm = nullptr; ch.gM = nullptr; ch.B = B; ch.rows = 3;
+    ch.sx_s = km_norm_scale(Ws); ch.sy_s = km_norm_scale(Hs); ch.sx_d = km_norm_scale(wd); ch.sy_d = km_norm_scale(hd);
+    hipLaunchKernelGGL(km_perspective_params_chain_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const float*)start_points,
+                       (const float*)end_points, (const float*)batch_prob, (float*)M_out, ch, (uint8_t*)apply);
+    return km_check_launch("km_perspective_params_chain_fwd");
+}
+
+// M (B,3,3) fp32 forward pixel matrix -> m_out (B,9) fp32, the normalised dst->src matrix of the INVERSE warp of an (H,W) image to its own
+// size; rows = 2 (warp_affine of Minv[:, :2]) or 3 (warp_perspective of Minv).
+int km_inverse_chain_fwd(const void* M, int rows, void* m_out, int B, int H, int W, void* stream) {
+    if (B == 0) return 0;
+    KM_REQUIRE(M && m_out, "km_inverse_chain_fwd: null pointer");
+    KM_REQUIRE(rows == 2 || rows == 3, "km_inverse_chain_fwd: rows must be 2 or 3, got %d", rows);
+    KM_REQUIRE(B > 0 && H > 0 && W > 0, "km_inverse_chain_fwd: bad sizes");
+    KmChainArgs<float> ch;
+    ch.M = nullptr; ch.A = nullptr; ch.m = (float*)m_out; ch.gm = nullptr; ch.gM = nullptr; ch.B = B; ch.rows = rows;
+    ch.sx_s = km_norm_scale(W); ch.sy_s = km_norm_scale(H); ch.sx_d = ch.sx_s; ch.sy_d = ch.sy_s;
+    hipLaunchKernelGGL(km_inverse_chain_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const float*)M, ch);
+    return km_check_launch("km_inverse_chain_fwd");
 }
 
 }  // extern "C"

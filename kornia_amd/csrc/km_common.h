@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#define KM_ABI_FEATURES 1  // km_abi_features(): bit 0 = km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd
 #define KM_ABI_VERSION 3  // include/kornia_amd.h, "Versioning": a library of version N exports the symbol sets of every version <= N
 
 // dtype codes of the C ABI (include/kornia_amd.h)
@@ -390,6 +391,10 @@ __device__ __forceinline__ int km_tid_pinned() {
 // The parity is per (device, stream); KM_TRAVERSAL=fixed / km_set_traversal(1) keeps every launch forward (A/B).
 uint32_t km_traversal_next(hipStream_t s);
 
+#ifndef KM_PAIR_FUSED_DEFAULT
+#define KM_PAIR_FUSED_DEFAULT 2  // km_warp2d_pair_fwd: 1 one launch (km_warp_pair_kernel), 0 two launches, 2 one launch for perspective / two for affine
+                                 // (what measured faster on each: profiles/README.md, r07)
+#endif
 // Launch policy, read once from the environment when the library is first used (km_runtime.hip); see profiles/README.md
 struct KmConfig {
     int traversal_fixed;    // KM_TRAVERSAL=fixed
@@ -401,6 +406,7 @@ struct KmConfig {
     int sg_generic;         // KM_SG_ALGO=generic
     int pyrdown_separable;  // KM_PYRDOWN_ALGO=separable
     int blur_rows;          // KM_BLUR_ROWS=8 / 16 / 32 (0: by storage type, direction, kernel size and size of the launch: km_blur_rows)
+    int pair_fused;         // KM_PAIR_ALGO=fused / two: km_warp2d_pair_fwd as one launch (image + first mask) or two; default KM_PAIR_FUSED_DEFAULT
     int warp_bwd_no_scan;   // KM_WARP_BWD_SCAN=0: the one-read backward does not look for non-finite gradients at output pixels that sample entirely outside the source
 };
 const KmConfig& km_config();

@@ -46,6 +46,8 @@ static void km_config_init() {
     const char* br = getenv("KM_BLUR_ROWS");
     c.blur_rows = br ? atoi(br) : 0;
     c.warp_bwd_no_scan = km_env_first("KM_WARP_BWD_SCAN", '0');
+    c.pair_fused = km_env_first("KM_PAIR_ALGO", 'f', 't');
+    c.pair_fused = c.pair_fused == 1 ? 1 : (c.pair_fused == 2 ? 0 : KM_PAIR_FUSED_DEFAULT);  // (f: 1, t: 0, unset: the default)
 }
 const KmConfig& km_config() {
     std::call_once(g_km_config_once, km_config_init);
@@ -166,6 +168,9 @@ extern "C" {
 
 int km_abi_version(void) { return KM_ABI_VERSION; }
 
+// entry points added after set 3, one bit per group (include/kornia_amd.h, Versioning)
+int km_abi_features(void) { return KM_ABI_FEATURES; }
+
 int km_stream_copy(const void* src, void* dst, long long bytes, int nontemporal, void* stream) {
     KM_REQUIRE(bytes >= 0 && bytes % 16 == 0, "km_stream_copy: bytes must be a non-negative multiple of 16");
     if (bytes == 0) return 0;
@@ -195,6 +200,7 @@ static int* km_config_field(const char* key) {
         {"warp_bwd_fused", &g_km_config.warp_bwd_fused},   {"sep_lds", &g_km_config.sep_lds},
         {"sg_generic", &g_km_config.sg_generic},           {"pyrdown_separable", &g_km_config.pyrdown_separable},
         {"blur_rows", &g_km_config.blur_rows},                 {"warp_bwd_no_scan", &g_km_config.warp_bwd_no_scan},
+        {"pair_fused", &g_km_config.pair_fused},
     };
     if (key)
         for (auto& e : table)
