@@ -31,7 +31,8 @@
  *   Entry points added after set 3 do not move the version (bindings written against set 3 pin it): each group of them is announced by a
  *   bit of `km_abi_features()`.  That symbol is itself new, so a binding looks it up with dlsym and treats its absence as 0.
  *     bit 0  km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd (masks, RandomPerspective and inverse() of the
- *            augmentation container).
+ *            augmentation container);
+ *     bit 1  km_crop_resize_fwd (crop_by_indices, RandomResizedCrop and the random flips).
  */
 #ifndef KORNIA_AMD_H
 #define KORNIA_AMD_H
@@ -183,6 +184,21 @@ enum { KM_MASK_BOOL = 0, KM_MASK_U8 = 1, KM_MASK_I32 = 2, KM_MASK_I64 = 3, KM_MA
 int km_warp2d_pair_fwd(const void* src, void* dst, const void* mask_src, void* mask_dst, const void* mat, const void* apply, int B, int C, int Cm,
                        int H, int W, int coord_mode, int interp, int pad, int align, const void* fill, const void* mask_fill, int dtype,
                        int mask_dtype, void* stream);
+
+/* [features bit 1] Batched crop -> resize (-> flip), kornia.geometry.transform.crop_by_indices (kornia/geometry/transform/crop2d.py:405-500)
+ * in one launch.  src (B,4,2) float32 corners (x, y) in the order top-left, top-right, bottom-right, bottom-left; sample b's window is
+ * [(long)src[b,0,1], (long)src[b,3,1] + 1) x [(long)src[b,0,0], (long)src[b,1,0] + 1), clamped to the image as Python slicing clamps it
+ * (never read outside the image); src NULL = the whole image, (oh, ow) must then be (H, W).  Per sample: a window of the output size is
+ * copied (bit for bit); otherwise compensation 0 resizes it - interp KM_BILINEAR: ATen's CPU upsample_bilinear2d with align_corners `align`,
+ * KM_NEAREST: ATen's CPU nearest_idx - and compensation 1 pads it with zeros / cuts it at the bottom and right (F.pad), except when every box
+ * of the batch is the same, which resizes as the reference does; an empty window gives zeros.  Flips: sample b is mirrored in x when bit 0
+ * of flip_all is set or flip_x[b] > 0.5, in y when bit 1 is set or flip_y[b] > 0.5 (torch.flip of the result, bit for bit); flip_x / flip_y
+ * (B) float32 (the flip modules' batch_prob draws) or NULL.  x / out (B,C,H,W) -> (B,C,oh,ow) in dtype (f32 /
+ * bf16 / f16), both NULL when C == 0 (dtype then names the image dtype of the masks' round trip); mask / mask_out (B,Cm,H,W) ->
+ * (B,Cm,oh,ow) in mask_dtype (KM_MASK_*), both NULL when Cm == 0: always nearest, through the image dtype and back, as in
+ * km_warp2d_pair_fwd.  Image and mask in one launch. */
+int km_crop_resize_fwd(const void* x, void* out, const void* mask, void* mask_out, const void* src, const void* flip_x, const void* flip_y,
+                       int flip_all, int B, int C, int Cm, int H, int W, int oh, int ow, int interp, int compensation, int align, int dtype, int mask_dtype, void* stream);
 
 /* ColorJitter's sampled factors -> the inputs of km_color_jitter_fwd(_masked) in one launch
  * (kornia/augmentation/_2d/intensity/color_jitter.py:137-148, base.py:380): brightness / contrast / saturation / hue (B) fp32

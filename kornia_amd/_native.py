@@ -75,9 +75,11 @@ _PROTOTYPES = {
     "km_warp2d_pair_fwd": [_P] * 6 + [_I] * 9 + [_P, _P, _I, _I, _P],
     "km_perspective_params_chain_fwd": [_P] * 6 + [_I] * 5 + [_P],
     "km_inverse_chain_fwd": [_P, _I, _P, _I, _I, _I, _P],
+    # km_abi_features() bit 1
+    "km_crop_resize_fwd": [_P] * 7 + [_I] * 13 + [_P],
 }
-ABI_FEATURES = 1  # the km_abi_features() bits this binding calls
-_FEATURE_SYMBOLS = {"km_warp2d_pair_fwd": 1, "km_perspective_params_chain_fwd": 1, "km_inverse_chain_fwd": 1}
+ABI_FEATURES = 3  # the km_abi_features() bits this binding calls
+_FEATURE_SYMBOLS = {"km_warp2d_pair_fwd": 1, "km_perspective_params_chain_fwd": 1, "km_inverse_chain_fwd": 1, "km_crop_resize_fwd": 2}
 KM_MASK_CODES = {torch.bool: 0, torch.uint8: 1, torch.int32: 2, torch.int64: 3, torch.float32: 4, torch.bfloat16: 5, torch.float16: 6}
 
 _lib: Optional[ctypes.CDLL] = None

@@ -24,7 +24,7 @@ third of a pixel in bfloat16).  No host synchronisation anywhere: t
 from __future__ import annotations
 
 import math
-from typing import Any, Mapping, Optional, Sequence
+from typing import Any, Mapping, Optional, Sequence, Tuple
 
 import torch
 
@@ -35,7 +35,8 @@ from .filters.gaussian import gaussian_blur2d
 from .geometry.transform.builders import get_affine_matrix2d, get_perspective_transform
 from .geometry.transform.imgwarp import COORD_PERSPECTIVE, _warp, _warp_affine_from_chain, warp_affine, warp_perspective
 
-__all__ = ["AugmentationSequential", "ColorJitter", "ParamItem", "RandomAffine", "RandomGaussianBlur", "RandomPerspective", "affine_chain", "affine_matrix",
+__all__ = ["AugmentationSequential", "ColorJitter", "ParamItem", "RandomAffine", "RandomGaussianBlur", "RandomHorizontalFlip", "RandomPerspective",
+           "RandomResizedCrop", "RandomVerticalFlip", "affine_chain", "affine_matrix",
            "apply_sequence", "color_jitter", "gaussian_taps", "inverse_chain", "perspective_chain", "random_affine", "random_gaussian_blur",
            "random_perspective", "select_samples", "warp_pair"]
 
@@ -330,7 +331,8 @@ def apply_sequence(input: torch.Tensor, affine: Mapping[str, Any], jitter: Mappi
 #     ``_params`` exposes host views with the reference's keys, so a replay through Kornia - or of Kornia's through this - works;
 #   * the apply step is the functions above: the per-sample probability switch inside the launches, no blend pass, no host synchronisation.
 # Round 7 adds RandomPerspective, label masks in the container (``data_keys`` with "mask" entries) and ``inverse()``; keypoints, boxes,
-# dictionaries, lists of masks and ``random_apply`` still raise.
+# dictionaries, lists of masks and ``random_apply`` still raise.  RandomResizedCrop and the two random flips run on the batched crop kernel
+# (``km_crop_resize_fwd``); flips right after a slice-mode crop ride in its launch, and children after a crop sample at its size.
 from collections import namedtuple
 
 ParamItem = namedtuple("ParamItem", ["name", "data"])  # (module name, parameter dictionary): what ``AugmentationSequential._params`` holds
@@ -816,6 +818,274 @@ class RandomGaussianBlur(_RandomOp):
         return random_gaussian_blur(x, params, self.kernel_size, self.border_type, self.separable)
 
 
+def _inv3x3(M: torch.Tensor) -> torch.Tensor:
+    """(B,3,3) -> the inverse by the adjugate, in torch float32 ops on M's device (no host synchronisation, no solver library)."""
+    a, b, c = M[:, :, 0], M[:, :, 1], M[:, :, 2]
+    r0, r1, r2 = torch.linalg.cross(b, c), torch.linalg.cross(c, a), torch.linalg.cross(a, b)
+    det = (a * r0).sum(-1).view(-1, 1, 1)
+    return torch.stack([r0, r1, r2], 1) / det
+
+
+class _CropFlipOp(_GeometricOp):
+    """What RandomResizedCrop and the two flips share: the image and the first mask in ONE launch of the batched crop -> resize (-> flip)
+    kernel (``km_crop_resize_fwd``, :func:`kornia_amd.geometry.transform.crop_resize`), further masks in mask-only launches, masks always nearest
+    and through the image dtype and back (augment.py:596-618)."""
+
+    _NATIVE_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+    def _crop(self, x: Optional[torch.Tensor], mask: Optional[torch.Tensor], p: Mapping[str, Any], image_dtype: torch.dtype, flips=(None, None, 0)):
+        raise NotImplementedError
+
+    def _flip_switch(self, p: Mapping[str, Any], device):
+        """(switch, bits): this flip's per-sample switch for the launch - its device ``batch_prob`` (thresholded in the launch) - or, when every
+        sample flips, None and the axis bit."""
+        if p.get("batch_prob") is None:
+            return None, self._AXIS_BIT
+        return _p(p, "batch_prob", device), 0
+
+    def _run(self, x: torch.Tensor, masks: list, p: Mapping[str, Any], image_dtype: torch.dtype, flips=(None, None, 0)):
+        if x.dtype not in self._NATIVE_DTYPES:
+            raise TypeError(f"{type(self).__name__}: the native crop / flip takes float32 / bfloat16 / float16 images, got {x.dtype}")
+        out, res = x, []
+        for k, mk in enumerate(masks):
+            o, mo = self._crop(x if k == 0 else None, mk, p, image_dtype, flips)
+            if k == 0:
+                out = o
+            res.append(mo)
+        if not masks:
+            out, _ = self._crop(x, None, p, image_dtype, flips)
+        return out, res
+
+    def _forward_masks(self, x: torch.Tensor, masks: list, params: Mapping[str, Any], own: bool, image_dtype: torch.dtype, flips=(None, None, 0)):
+        if not own:
+            self._st["host_buf"] = None
+        self._st["params"] = dict(params)
+        self._st["device"] = x.device
+        p = self._device_params(self._st["params"], x.device, own)
+        if torch.is_grad_enabled() and x.requires_grad:  # the image through the differentiable composition, the masks through the kernel
+            return self._apply(x, p), self._run(x.detach(), masks, p, image_dtype)[1]
+        return self._run(x, masks, p, image_dtype, flips)
+
+    def _params_for_device(self, params: Mapping[str, Any], own: bool, device) -> dict:
+        """A fused child's share of the call (the container folds it into the crop's launch): the state a call leaves, the device parameters."""
+        if not own:
+            self._st["host_buf"] = None
+        self._st["params"] = dict(params)
+        self._st["device"] = device
+        return self._device_params(self._st["params"], device, own)
+
+
+class RandomResizedCrop(_CropFlipOp):
+    """``kornia.augmentation.RandomResizedCrop`` (kornia/augmentation/_2d/geometric/resized_crop.py:28-170, random_generator/_2d/crop.py:36-291) on
+    the native path: the same constructor, parameter keys and draws (``ResizedCropGenerator`` then ``CropGenerator``, restated in host float32
+    torch), ``cropping_mode="slice"`` as ONE launch of the batched crop -> resize for the image and its first mask (flips that follow it in a
+    container ride in the same launch), ``"resample"`` as ``crop_by_transform_mat`` (the native warp).  Refused: ``p < 1`` (the reference's
+    batch-level gate would return some batches at another size) and ``inverse()`` in slice mode (as in the reference)."""
+
+    _FLOATS_PER_SAMPLE = 17  # batch_prob, src (8), dst (8)
+
+    def __init__(self, size: Tuple[int, int], scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), resample="BILINEAR", same_on_batch: bool = False,
+                 align_corners: bool = True, p: float = 1.0, keepdim: bool = False, cropping_mode: str = "slice") -> None:
+        super().__init__(1.0, same_on_batch, keepdim, p_batch=p)
+        if not (len(size) == 2 and isinstance(size[0], int) and isinstance(size[1], int) and size[0] > 0 and size[1] > 0):
+            raise AssertionError(f"`output_size` must be a tuple of 2 positive integers. Got {size}.")
+        self.scale = self._range_check(scale, "scale")
+        self.ratio = self._range_check(ratio, "ratio")
+        self._scale_arg, self._ratio_arg = scale, ratio
+        if float(p) < 1.0:
+            raise NotImplementedError(f"RandomResizedCrop: p={p} < 1 (the reference's batch-level gate: a batch left alone keeps its size, another "
+                                      "is cropped) is not supported on the native path")
+        if cropping_mode not in ("slice", "resample"):
+            raise NotImplementedError(f"Not supported type: {cropping_mode}.")
+        self.size = (int(size[0]), int(size[1]))
+        self.resample = str(getattr(resample, "name", resample)).lower()
+        if self.resample not in ("bilinear", "nearest"):
+            raise NotImplementedError(f"RandomResizedCrop: resample={resample!r} - the native path resamples 'bilinear' or 'nearest'")
+        self.align_corners = bool(align_corners)
+        self.cropping_mode = cropping_mode
+        self.padding_mode = "zeros"
+        self.fill_value = None
+
+    @staticmethod
+    def _range_check(v, name: str) -> torch.Tensor:
+        t = torch.as_tensor(v, dtype=torch.float32)
+        # (_joint_range_check, kornia/augmentation/utils/param_validation.py:106-119, with unbounded limits)
+        if not (t.dim() == 1 and len(t) == 2):
+            raise TypeError(f"{name} should be a torch.Tensor with length 2 whose values between {(float('-inf'), float('inf'))}. Got {t}.")
+        if not float(t[0]) <= float(t[1]):
+            raise ValueError(f"{name}[0] should be smaller than {name}[1] got {t}")
+        return t
+
+    def _sample(self, d: _Draws, shape, params: dict) -> None:
+        # ResizedCropGenerator.forward (crop.py:224-291) then CropGenerator.forward (:81-170), operation for operation in float32
+        B, H, W = int(shape[0]), int(shape[-2]), int(shape[-1])
+        src, dst = d.piece(B, 4, 2), d.piece(B, 4, 2)
+        same = self.same_on_batch
+
+        def rand(*shp):
+            r = torch.rand(1 if same else B, *shp, dtype=torch.float32)
+            return r.repeat(B, *([1] * len(shp))) if same else r
+
+        rand_tensor = rand(10)  # (Uniform(0, 1).rsample: 0 + r * 1, the same bits)
+        area = (rand_tensor * (self.scale[1] - self.scale[0]) + self.scale[0]) * H * W
+        lo, hi = torch.log(self.ratio[0]), torch.log(self.ratio[1])
+        aspect_ratio = torch.exp(lo + rand(10) * (hi - lo))
+        w = torch.sqrt(area * aspect_ratio).round().floor()
+        h = torch.sqrt(area / aspect_ratio).round().floor()
+        cond = ((0 < w) * (w < W) * (0 < h) * (h < H)).int()
+        cond_bool, argmax_dim1 = ((cond.cumsum(1) == 1) & cond.bool()).max(1)
+        rows = torch.arange(0, B, dtype=torch.long)
+        h_out, w_out = h[rows, argmax_dim1], w[rows, argmax_dim1]
+        in_ratio = float(H) / float(W)
+        _min = float(self._ratio_arg.min()) if isinstance(self._ratio_arg, torch.Tensor) else min(self._ratio_arg)
+        if in_ratio < _min:
+            h_ct = torch.tensor(H, dtype=torch.float32)
+            w_ct = torch.round(h_ct / _min)
+        elif in_ratio > _min:
+            w_ct = torch.tensor(W, dtype=torch.float32)
+            h_ct = torch.round(w_ct * _min)
+        else:
+            h_ct, w_ct = torch.tensor(H, dtype=torch.float32), torch.tensor(W, dtype=torch.float32)
+        h_out = torch.clamp(torch.where(cond_bool, h_out, h_ct.floor()), min=1, max=H)
+        w_out = torch.clamp(torch.where(cond_bool, w_out, w_ct.floor()), min=1, max=W)
+        size = torch.stack([h_out, w_out], dim=1).floor()
+        x_diff = (W - size[:, 1] + 1).clamp(0)
+        y_diff = (H - size[:, 0] + 1).clamp(0)
+        if same:
+            x_start = (rand() * x_diff[0]).floor()
+            y_start = (rand() * y_diff[0]).floor()
+        else:
+            x_start = (rand() * x_diff).floor()
+            y_start = (rand() * y_diff).floor()
+        cw = torch.where(size[:, 1] == 0, torch.tensor(W, dtype=torch.float32), size[:, 1])
+        ch = torch.where(size[:, 0] == 0, torch.tensor(H, dtype=torch.float32), size[:, 0])
+        x0, y0 = x_start.view(-1), y_start.view(-1)
+        x1, y1 = x0 + cw - 1, y0 + ch - 1
+        torch.stack([torch.stack([x0, y0], -1), torch.stack([x1, y0], -1), torch.stack([x1, y1], -1), torch.stack([x0, y1], -1)], -2, out=src)
+        oh, ow = self.size
+        geo = self._st.get("geo")
+        if geo is None or geo[0] != (B, H, W):  # (the constant tensors of this batch shape, formed once)
+            geo = self._st["geo"] = ((B, H, W), torch.tensor([[[0.0, 0.0], [ow - 1, 0.0], [ow - 1, oh - 1], [0.0, oh - 1]]], dtype=torch.float32),
+                                     torch.tensor((H, W), dtype=torch.long).expand(B, -1), torch.tensor(self.size, dtype=torch.long).expand(B, -1))
+        dst.copy_(geo[1].expand(B, 4, 2))
+        params.update(src=src, dst=dst, input_size=geo[2], output_size=geo[3])
+
+    def _matrix(self, p: Mapping[str, Any], device) -> torch.Tensor:
+        return get_perspective_transform(_p(p, "src", device), _p(p, "dst", device))
+
+    def _crop(self, x, mask, p, image_dtype, flips=(None, None, 0)):
+        from .geometry.transform.crop2d import crop_resize
+
+        ref = x if x is not None else mask
+        if self.cropping_mode == "slice":
+            if self.resample == "nearest" and x is not None:
+                raise ValueError("align_corners option can only be set with the interpolating modes: linear | bilinear | bicubic | trilinear")
+            return crop_resize(x, mask, _p(p, "src", ref.device), self.size, self.resample, self.align_corners, "resize", *flips, image_dtype=image_dtype)
+        # resample: the warp of the box's matrix to the output size (crop_by_transform_mat), masks nearest with the module's align_corners
+        M = self._matrix(p, ref.device)[:, :2, :]
+        out = warp_affine(x, M, self.size, self.resample, "zeros", self.align_corners) if x is not None else None
+        mout = None
+        if mask is not None:
+            mout = warp_affine(mask.to(image_dtype), M, self.size, "nearest", "zeros", self.align_corners).to(mask.dtype)
+        return out, mout
+
+    def _apply(self, x: torch.Tensor, params: dict) -> torch.Tensor:
+        from .geometry.transform.crop2d import crop_by_indices, crop_by_transform_mat
+
+        if torch.is_grad_enabled() and x.requires_grad:
+            if self.cropping_mode == "slice":
+                return crop_by_indices(x, _p(params, "src", x.device), self.size, self.resample, self.align_corners)
+            return crop_by_transform_mat(x, self._matrix(params, x.device)[:, :2, :], self.size, self.resample, "zeros", self.align_corners)
+        return self._run(x, [], params, x.dtype)[0]
+
+    def _inverse_masks(self, x: torch.Tensor, masks: list, params: Mapping[str, Any], image_dtype: torch.dtype):
+        """resized_crop.py:146-170: the warp of the inverse matrix back to the input size (resample mode only)."""
+        if self.cropping_mode != "resample":
+            raise NotImplementedError(f"`inverse` is only applicable for resample cropping mode. Got {self.cropping_mode}.")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("inverse() is forward-only here (no autograd through the inverse warp)")
+        p = self._device_params(dict(params), x.device, False)
+        shp = torch.as_tensor(params["forward_input_shape"]).tolist()
+        size = (int(shp[-2]), int(shp[-1]))
+        Minv = _inv3x3(self._matrix(p, x.device))[:, :2, :]
+        out = warp_affine(x, Minv, size, self.resample, "zeros", self.align_corners)
+        return out, [warp_affine(mk.to(image_dtype), Minv, size, "nearest", "zeros", self.align_corners).to(mk.dtype) for mk in masks]
+
+    @property
+    def transform_matrix(self) -> Optional[torch.Tensor]:
+        """(B,3,3) ``get_perspective_transform(src, dst)`` of the last call, on the device of the last input."""
+        if not self._params:
+            return None
+        return self._matrix(self._params, self._st.get("device") or torch.device("cuda"))
+
+
+class _RandomFlip(_CropFlipOp):
+    """A random flip on the native path: one launch of the batched crop kernel with the whole image as the window, the per-sample switch
+    (``batch_prob > 0.5``) read inside the launch; its own inverse."""
+
+    _FLOATS_PER_SAMPLE = 1  # batch_prob
+    _AXIS_BIT = 1
+    _DIM = -1
+
+    def __init__(self, p: float = 0.5, same_on_batch: bool = False, keepdim: bool = False) -> None:
+        super().__init__(p, same_on_batch, keepdim)
+        self.resample, self.align_corners, self.padding_mode, self.fill_value = "nearest", False, "zeros", None
+
+    def _sample(self, d: _Draws, shape, params: dict) -> None:
+        return None  # (the probability draw is all a flip samples)
+
+    def _crop(self, x, mask, p, image_dtype, flips=(None, None, 0)):
+        from .geometry.transform.crop2d import crop_resize
+
+        ref = x if x is not None else mask
+        sw, bits = self._flip_switch(p, ref.device)
+        fx, fy = (sw, None) if self._AXIS_BIT == 1 else (None, sw)
+        return crop_resize(x, mask, None, tuple(ref.shape[-2:]), "nearest", False, "resize", fx, fy, bits, image_dtype=image_dtype)
+
+    def _apply(self, x: torch.Tensor, params: dict) -> torch.Tensor:
+        if torch.is_grad_enabled() and x.requires_grad:
+            return select_samples(torch.flip(x, [self._DIM]), x, _apply_mask(params, x.device))
+        return self._run(x, [], params, x.dtype)[0]
+
+    def _inverse_masks(self, x: torch.Tensor, masks: list, params: Mapping[str, Any], image_dtype: torch.dtype):
+        """horizontal_flip.py:96-115: the same flip again (samples whose draw failed pass through)."""
+        p = self._device_params(dict(params), x.device, False)
+        if torch.is_grad_enabled() and x.requires_grad:
+            return self._apply(x, p), self._run(x.detach(), masks, p, image_dtype)[1]
+        return self._run(x, masks, p, image_dtype)
+
+    @property
+    def transform_matrix(self) -> Optional[torch.Tensor]:
+        """(B,3,3) the reference's flip matrix (``[[-1, 0, w - 1], [0, 1, 0], [0, 0, 1]]`` horizontally, the vertical one likewise) of the last
+        call, the identity for the samples whose probability draw failed, on the device of the last input."""
+        if not self._params:
+            return None
+        shp = torch.as_tensor(self._params["forward_input_shape"]).tolist()
+        dev = self._st.get("device") or torch.device("cuda")
+        M = torch.eye(3, dtype=torch.float32)
+        k = 0 if self._AXIS_BIT == 1 else 1
+        M[k, k], M[k, 2] = -1.0, float(shp[-1] if k == 0 else shp[-2]) - 1.0
+        M = M.to(dev).expand(int(shp[0]), 3, 3)
+        apply = _apply_mask(self._params, dev)
+        if apply is not None:
+            M = torch.where(apply.view(-1, 1, 1), M, torch.eye(3, device=dev).expand_as(M))
+        return M
+
+
+class RandomHorizontalFlip(_RandomFlip):
+    """``kornia.augmentation.RandomHorizontalFlip`` (kornia/augmentation/_2d/geometric/horizontal_flip.py:27-115) on the native path."""
+
+    _AXIS_BIT = 1
+    _DIM = -1
+
+
+class RandomVerticalFlip(_RandomFlip):
+    """``kornia.augmentation.RandomVerticalFlip`` (kornia/augmentation/_2d/geometric/vertical_flip.py:26-105) on the native path."""
+
+    _AXIS_BIT = 2
+    _DIM = -2
+
+
 _MASK_REFUSED = ("keypoints, boxes, dictionaries, lists of masks and random_apply are not supported here; use Kornia's container with "
                  "kornia_amd.patch()")
 
@@ -840,7 +1110,8 @@ class AugmentationSequential(torch.nn.Module):
             raise NotImplementedError(f"random_apply: {_MASK_REFUSED}")
         for i, m in enumerate(args):
             if not isinstance(m, _RandomOp):
-                raise NotImplementedError(f"child {i} ({type(m).__name__}) is not one of this package's modules (RandomAffine, RandomPerspective, ColorJitter, RandomGaussianBlur)")
+                raise NotImplementedError(f"child {i} ({type(m).__name__}) is not one of this package's modules (RandomAffine, RandomPerspective, "
+                                          "RandomResizedCrop, RandomHorizontalFlip, RandomVerticalFlip, ColorJitter, RandomGaussianBlur)")
             if same_on_batch is not None:
                 m.same_on_batch = bool(same_on_batch)
             if keepdim is not None:
@@ -851,7 +1122,42 @@ class AugmentationSequential(torch.nn.Module):
         object.__setattr__(self, "_draws", None)
         object.__setattr__(self, "_kids", list(self.named_children()))
         object.__setattr__(self, "_keys", keys)
+        object.__setattr__(self, "_fusion", self._plan_fusion())
         self._check_masks(keys)
+
+    def _plan_fusion(self) -> dict:
+        """{index of a slice-mode RandomResizedCrop: indices of the flips directly after it (one horizontal, one vertical at most)}: their
+        per-sample switches ride in the crop's launch."""
+        plan = {}
+        kids = self._kids
+        for i, (_, m) in enumerate(kids):
+            if type(m) is RandomResizedCrop and m.cropping_mode == "slice":
+                group, axes = [], 0
+                for j in range(i + 1, len(kids)):
+                    f = kids[j][1]
+                    if not isinstance(f, _RandomFlip) or axes & f._AXIS_BIT:
+                        break
+                    group.append(j)
+                    axes |= f._AXIS_BIT
+                if group:
+                    plan[i] = group
+        return plan
+
+    def _fused(self, i: int, x: torch.Tensor, masks: list, params, own: bool, image_dtype: torch.dtype):
+        """Child i (a slice-mode crop) and the flips after it as ONE launch for the image and the first mask: each flip's call state is what
+        its own call would leave, its device ``batch_prob`` the switch the launch reads.  Returns (x, masks, the next child's index)."""
+        group = self._fusion[i]
+        flips = [None, None, 0]
+        for j in group:
+            f = self._kids[j][1]
+            sw, bits = f._flip_switch(f._params_for_device(params[j].data, own, x.device), x.device)
+            flips[0 if f._AXIS_BIT == 1 else 1] = sw
+            flips[2] |= bits
+        x, masks = self._kids[i][1]._forward_masks(x, masks, params[i].data, own, image_dtype, tuple(flips))
+        return x, masks, group[-1] + 1
+
+    def _can_fuse(self, i: int, x: torch.Tensor) -> bool:
+        return i in self._fusion and not (torch.is_grad_enabled() and x.requires_grad) and x.dtype in _CropFlipOp._NATIVE_DTYPES
 
     @staticmethod
     def _parse_keys(data_keys) -> list:
@@ -866,12 +1172,19 @@ class AugmentationSequential(torch.nn.Module):
         return keys
 
     def forward_parameters(self, batch_shape) -> list:
-        """One ``ParamItem`` per child, sampled in order (a same-size pipeline: every child sees the input's shape); the draws of ALL children
-        in one host buffer."""
+        """One ``ParamItem`` per child, sampled in order; the draws of ALL children in one host buffer.  A child whose parameters carry
+        ``output_size`` (RandomResizedCrop) changes the shape the children after it sample at (the reference's ``_get_new_batch_shape``,
+        container/image.py:401)."""
         B = int(batch_shape[0])
         children = self._kids
         d = _Draws(sum(m._FLOATS_PER_SAMPLE for _, m in children) * B)
-        items = [ParamItem(name, m.forward_parameters(batch_shape, d)) for name, m in children]
+        items = []
+        for name, m in children:
+            prm = m.forward_parameters(batch_shape, d)
+            items.append(ParamItem(name, prm))
+            osz = prm.get("output_size")
+            if osz is not None:
+                batch_shape = (*tuple(batch_shape)[:-2], *(int(v) for v in osz[0].tolist()))
         object.__setattr__(self, "_draws", d)
         return items
 
@@ -966,22 +1279,45 @@ class AugmentationSequential(torch.nn.Module):
             input = args[0]
             params, own = self._prepare(input, params)
             out, used = input, []
-            for i, (name, m) in enumerate(children):
-                out = m(out, params[i].data, _own=own)
-                used.append(ParamItem(name, m._params))
+            if not self._fusion:
+                for i, (name, m) in enumerate(children):
+                    out = m(out, params[i].data, _own=own)
+                    used.append(ParamItem(name, m._params))
+                object.__setattr__(self, "_params", used)
+                return out
+            x = out.unsqueeze(0) if out.dim() == 3 else out
+            i = 0
+            while i < len(children):
+                if self._can_fuse(i, x):
+                    x, _, nxt = self._fused(i, x, [], params, own, x.dtype)
+                    used += [ParamItem(children[j][0], children[j][1]._params) for j in range(i, nxt)]
+                    i = nxt
+                    continue
+                x = children[i][1](x, params[i].data, _own=own)
+                used.append(ParamItem(children[i][0], children[i][1]._params))
+                i += 1
             object.__setattr__(self, "_params", used)
-            return out
+            keep = input.dim() == 3 and any(m.keepdim for _, m in children)
+            return x[0] if keep else x
         img = args[keys.index("input")] if len(args) == len(keys) else args[0]
         params, own = self._prepare(img.unsqueeze(0) if img.dim() == 3 else img, params)
 
         def walk(x, masks, image_dtype):
             used = []
-            for i, (name, m) in enumerate(children):
+            i = 0
+            while i < len(children):
+                name, m = children[i]
+                if self._can_fuse(i, x):
+                    x, masks, nxt = self._fused(i, x, masks, params, own, image_dtype)
+                    used += [ParamItem(children[j][0], children[j][1]._params) for j in range(i, nxt)]
+                    i = nxt
+                    continue
                 if m._GEOMETRIC:
                     x, masks = m._forward_masks(x, masks, params[i].data, own, image_dtype)
                 else:
                     x = m(x, params[i].data, _own=own)
                 used.append(ParamItem(name, m._params))
+                i += 1
             object.__setattr__(self, "_params", used)
             return x, masks
 

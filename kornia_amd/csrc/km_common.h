@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define KM_ABI_FEATURES 1  // km_abi_features(): bit 0 = km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd
+#define KM_ABI_FEATURES 3  // km_abi_features(): bit 0 = km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd; bit 1 = km_crop_resize_fwd
 #define KM_ABI_VERSION 3  // include/kornia_amd.h, "Versioning": a library of version N exports the symbol sets of every version <= N
 
 // dtype codes of the C ABI (include/kornia_amd.h)

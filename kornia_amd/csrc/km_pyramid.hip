@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "km_regtile.h"
+#include "km_resize_axis.h"
 
 
 
@@ -32,25 +33,6 @@ __device__ __forceinline__ float kmp_round(float v, const float*) { return v; }
 __device__ __forceinline__ double kmp_round(double v, const double*) { return v; }
 __device__ __forceinline__ float kmp_round(float v, const km_bf16*) { return __uint_as_float(((uint32_t)km_f32_to_bf16_bits(v)) << 16); }
 __device__ __forceinline__ float kmp_round(float v, const km_f16*) { KM_OPAQUE(v); return (float)(km_f16)v; }
-
-// ATen area_pixel_compute_scale / area_pixel_compute_source_index (bilinear: negative sources clamp to 0)
-template <typename R>
-__device__ __forceinline__ void kmp_axis(int d, int n_in, int n_out, int align, int& i0, int& i1, R& l0, R& l1) {
-    R src;
-    if (align) {
-        const R scale = n_out > 1 ? (R)(n_in - 1) / (R)(n_out - 1) : (R)0;
-        src = scale * (R)d;
-    } else {
-        const R scale = (R)n_in / (R)n_out;
-        src = scale * ((R)d + (R)0.5) - (R)0.5;
-        if (src < (R)0) src = (R)0;
-    }
-    i0 = (int)src;
-    if (i0 > n_in - 1) i0 = n_in - 1;
-    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    l1 = src - (R)i0;
-    l0 = (R)1 - l1;
-}
 
 template <typename T>
 struct KmPyrArgs {

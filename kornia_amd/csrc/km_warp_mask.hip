@@ -19,53 +19,7 @@
 // pixel for both) or in TWO - the image through km_warp2d_fwd_masked, its kernels untouched, then this kernel on the same matrix and
 // switch; the image is bit-identical to km_warp2d_fwd_masked either way.  Which one runs: KM_PAIR_FUSED_DEFAULT (km_common.h).
 #include "km_warp_args.h"
-
-enum { KM_MASK_BOOL = 0, KM_MASK_U8 = 1, KM_MASK_I32 = 2, KM_MASK_I64 = 3, KM_MASK_F32 = 4, KM_MASK_BF16 = 5, KM_MASK_F16 = 6 };
-
-template <int MD> struct KmMaskStore;
-template <> struct KmMaskStore<KM_MASK_BOOL> { typedef uint8_t T; };
-template <> struct KmMaskStore<KM_MASK_U8> { typedef uint8_t T; };
-template <> struct KmMaskStore<KM_MASK_I32> { typedef int32_t T; };
-template <> struct KmMaskStore<KM_MASK_I64> { typedef long long T; };
-template <> struct KmMaskStore<KM_MASK_F32> { typedef float T; };
-template <> struct KmMaskStore<KM_MASK_BF16> { typedef km_bf16 T; };
-template <> struct KmMaskStore<KM_MASK_F16> { typedef km_f16 T; };
-
-// mask element -> float (an integer wider than 24 bits rounds here, as c10's conversion of an integer to Half / BFloat16 does: via float)
-template <int MD>
-__device__ __forceinline__ float km_mask_ld(const typename KmMaskStore<MD>::T* p) {
-    if constexpr (MD == KM_MASK_BOOL) return *p != 0 ? 1.0f : 0.0f;
-    else if constexpr (MD == KM_MASK_U8 || MD == KM_MASK_I32 || MD == KM_MASK_I64) return (float)(*p);
-    else return km_ld(p);
-}
-
-// float -> the image's storage type -> float (_preproc_mask's cast, and the warp's own store)
-template <int DT>
-__device__ __forceinline__ float km_img_round(float v) {
-    if constexpr (DT == KM_F32) return v;
-    else if constexpr (DT == KM_BF16) return __uint_as_float(((uint32_t)km_f32_to_bf16_bits(v)) << 16);
-    else {
-        km_f16 h;
-        km_st(&h, v);
-        return km_ld(&h);
-    }
-}
-
-// an image-dtype value (as float) -> the mask's storage type (_postproc_mask): c10's casts - uint8 through int64, the other integers
-// truncate toward zero, bool is != 0, the float types round to nearest even
-template <int MD>
-__device__ __forceinline__ typename KmMaskStore<MD>::T km_mask_cast(float v) {
-    typedef typename KmMaskStore<MD>::T M;
-    if constexpr (MD == KM_MASK_BOOL) return (M)(v != 0.0f ? 1 : 0);
-    else if constexpr (MD == KM_MASK_U8) return (M)(long long)v;
-    else if constexpr (MD == KM_MASK_I32 || MD == KM_MASK_I64) return (M)v;
-    else if constexpr (MD == KM_MASK_F32) return v;
-    else {
-        M out;
-        km_st(&out, v);
-        return out;
-    }
-}
+#include "km_mask.h"
 
 struct KmMaskArgs {
     const void* src;         // (B,Cm,H,W) mask dtype
@@ -159,11 +113,6 @@ static void km_warp_mask_launch(const KmMaskArgs& a0, hipStream_t s) {
 // any padding: the generic forward's arithmetic, which the specialised forwards reproduce bit for bit) and for every mask channel
 // (nearest, as above).  Image stores: 64 consecutive pixels per wave instruction, as the generic forward; mask stores: 64 consecutive
 // elements (64 B for 1-byte masks).  Bicubic images take the two-launch form.
-template <int DT> struct KmImgT;
-template <> struct KmImgT<KM_F32> { typedef float T; };
-template <> struct KmImgT<KM_BF16> { typedef km_bf16 T; };
-template <> struct KmImgT<KM_F16> { typedef km_f16 T; };
-
 template <int MD, int DT, int CM, int INTERP>
 __global__ __launch_bounds__(256) void km_warp_pair_kernel(const KmMaskArgs a) {
     typedef typename KmMaskStore<MD>::T M;

@@ -8,7 +8,7 @@ from .builders import (
     get_shear_matrix2d,
     get_translation_matrix2d,
 )
-from .crop2d import center_crop, crop_and_resize, crop_by_boxes, crop_by_transform_mat
+from .crop2d import center_crop, crop_and_resize, crop_by_boxes, crop_by_indices, crop_by_transform_mat
 from .homography_warper import HomographyWarper
 from .pyramid import PyrDown, PyrUp, ScalePyramid, build_laplacian_pyramid, build_pyramid, pyrdown, pyrup, resize_bilinear
 from .image_registrator import BaseModel, Homography, ImageRegistrator, Similarity, masked_warp_loss
@@ -36,6 +36,7 @@ __all__ = [
     "center_crop",
     "crop_and_resize",
     "crop_by_boxes",
+    "crop_by_indices",
     "crop_by_transform_mat",
     "rotate",
     "scale",
