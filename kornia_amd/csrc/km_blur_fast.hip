@@ -14,6 +14,12 @@
 //            ZERO-extended gradient with position-dependent taps  W[p][i] = sum_t k[t] [map(i+t-l) == p]
 //            which differ from the flipped taps only within K-1 pixels of a border (the pad fold).
 //            Circular is periodic: unmodified flipped taps on periodic indexing.
+//            fp32: row adjoint per input row into the ring, column adjoint over the ring.  16-bit (COLF): the
+//            reference's order - its autograd runs the column pass's adjoint first and holds that gradient in the
+//            storage dtype - so the ring holds grad_out rows, the column adjoint is rounded to T, and the row
+//            adjoint reads the neighbouring columns of that result from the neighbour lanes.  (16-bit circular
+//            adjoints take the LDS kernel: km_blur_fast_bwd_supported.)  Cost: none measurable - bf16, 256x3x224^2, K = 5,
+//            rocprofv3 on one MI355X: 90.0 us mean (87.8 min) column-first against 90.7 (86.6) for the row-first form.
 //
 // Requirements checked by the host: K odd, 3 <= K <= 9, kW == kH == K, 'same' padding, W % 4 == 0,
 // W >= 8, H >= K, 16-byte aligned planes.  Everything else takes the generic LDS kernel.
@@ -106,6 +112,7 @@ __device__ __forceinline__ void kmb_adjoint_taps(const float (&k)[K], int p, int
 template <typename T, int K, bool BWD, int ROWS = KMB_ROWS>
 __global__ __launch_bounds__(256, (BWD ? KMB_BWD_WAVES : 1)) void km_blur_reg_kernel(const KmBlurArgs<T> a) {
     constexpr int L = (K - 1) / 2, R = K - 1 - L;
+    constexpr bool COLF = BWD && sizeof(T) == 2;  // column adjoint first, rounded to T (see the head of the file)
     uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks, a.reverse);
     const uint32_t tbx = bid % a.bx;
     bid /= a.bx;
@@ -141,7 +148,9 @@ __global__ __launch_bounds__(256, (BWD ? KMB_BWD_WAVES : 1)) void km_blur_reg_ke
     if (left) offL = (border == KM_BORDER_CIRCULAR) ? W - 4 : c0;
     if (right) offR = (border == KM_BORDER_CIRCULAR) ? 0 : c0;
 
-    float ring[K][4];  // rolling window of row-pass results
+    float ring[K][4];  // rolling window of row-pass results (COLF: of grad_out rows)
+    // COLF: the R columns of the edge chunk that the row adjoint of lane 0 (left of it) / lane 63 (right of it) reads, per window row
+    float ring_e[COLF ? K : 1][COLF ? R : 1];
     const int n_rows = (r0 + ROWS <= H ? ROWS : H - r0);
     const int total = n_rows + K - 1;
     const bool e0 = (lane == 0), e63 = (lane == 63);
@@ -218,24 +227,72 @@ __global__ __launch_bounds__(256, (BWD ? KMB_BWD_WAVES : 1)) void km_blur_reg_ke
                     for (int q = 0; q < 12; ++q) v[q] = 0.f;
                 }
                 // v[i] holds column c0 - 4 + i
+                if constexpr (COLF) {
+                    // the row adjoint waits for the column adjoint: keep the row (zero outside the image) and the edge columns lane 0 / 63 need
 #pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    float acc = 0.f;
-                    if (BWD) {
-                        // taps wx[o][d] multiply column (c0+o) - R + d
+                    for (int o = 0; o < 4; ++o) ring[kk][o] = v[4 + o];
 #pragma unroll
-                        for (int d = 0; d < K; ++d) acc = km_fma(wx[o][d], v[4 + o - R + d], acc);
-                    } else {
+                    for (int j = 0; j < R; ++j) ring_e[kk][j] = e0 ? v[4 - R + j] : v[8 + j];
+                } else {
 #pragma unroll
-                        for (int q = 0; q < K; ++q) acc = km_fma(kx[q], v[4 + o - L + q], acc);
+                    for (int o = 0; o < 4; ++o) {
+                        float acc = 0.f;
+                        if (BWD) {
+                            // taps wx[o][d] multiply column (c0+o) - R + d
+#pragma unroll
+                            for (int d = 0; d < K; ++d) acc = km_fma(wx[o][d], v[4 + o - R + d], acc);
+                        } else {
+#pragma unroll
+                            for (int q = 0; q < K; ++q) acc = km_fma(kx[q], v[4 + o - L + q], acc);
+                        }
+                        ring[kk][o] = km_round_store(acc, (const T*)nullptr);
                     }
-                    ring[kk][o] = km_round_store(acc, (const T*)nullptr);
                 }
                 // ---- column pass: emits output row r = r0 + it - (K-1) once K rows are in the window ----
                 if (it >= K - 1) {
                     const int r = r0 + it - (K - 1);
                     float res[4];
-                    if (BWD) {
+                    if constexpr (COLF) {
+                        float wy[K];
+                        kmb_adjoint_taps<K>(ky, r, H, border, wy);
+                        float c4[4], ce[R];
+#pragma unroll
+                        for (int o = 0; o < 4; ++o) {
+                            float acc = 0.f;
+#pragma unroll
+                            for (int d = 0; d < K; ++d) acc = km_fma(wy[d], ring[(kk + 1 + d) % K][o], acc);
+                            c4[o] = km_round_store(acc, (const T*)nullptr);
+                        }
+#pragma unroll
+                        for (int j = 0; j < R; ++j) {
+                            float acc = 0.f;
+#pragma unroll
+                            for (int d = 0; d < K; ++d) acc = km_fma(wy[d], ring_e[(kk + 1 + d) % K][j], acc);
+                            ce[j] = km_round_store(acc, (const T*)nullptr);
+                        }
+                        // row adjoint of the rounded column adjoint: columns c0 - 4 .. c0 + 7, the outer ones from the neighbour lanes
+                        // (lane 0 / 63: their own edge columns), zero beyond the image
+                        float u[12];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const float pl = km_prev64(c4[q]), nr = km_next64(c4[q]);
+                            u[q] = left ? 0.f : pl;
+                            u[4 + q] = c4[q];
+                            u[8 + q] = right ? 0.f : nr;
+                        }
+#pragma unroll
+                        for (int j = 0; j < R; ++j) {
+                            if (e0 && !left) u[4 - R + j] = ce[j];
+                            if (e63 && !right) u[8 + j] = ce[j];
+                        }
+#pragma unroll
+                        for (int o = 0; o < 4; ++o) {
+                            float acc = 0.f;
+#pragma unroll
+                            for (int d = 0; d < K; ++d) acc = km_fma(wx[o][d], u[4 + o - R + d], acc);
+                            res[o] = acc;
+                        }
+                    } else if (BWD) {
                         float wy[K];
                         kmb_adjoint_taps<K>(ky, r, H, border, wy);
 #pragma unroll
@@ -322,6 +379,13 @@ int km_blur_fast_supported(const void* x, const void* y, int H, int W, int kH, i
     if (((uintptr_t)x % (4 * esz)) != 0 || ((uintptr_t)y % (4 * esz)) != 0) return 0;
     if ((((size_t)H * W * esz) % (4 * esz)) != 0) return 0;
     return 1;
+}
+
+// 1 if the register-tiled ADJOINT handles this problem: as above, except 16-bit circular borders (the column-first form takes the
+// neighbouring columns of a row from the neighbour lanes; a periodic row would need the wrapped chunk at both ends of a wave)
+int km_blur_fast_bwd_supported(const void* gy, const void* gx, int H, int W, int kH, int kW, int border, int same, int dtype) {
+    if (dtype != KM_F32 && border == KM_BORDER_CIRCULAR) return 0;
+    return km_blur_fast_supported(gy, gx, H, W, kH, kW, border, same, dtype);
 }
 
 int km_blur_fast_run(bool bwd, const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk, int K,

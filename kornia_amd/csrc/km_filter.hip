@@ -545,6 +545,7 @@ int km_filter2d_fast_run(const void* x, const void* k, void* y, int B, int C, in
 
 // register-tiled fast path for small square odd kernels (km_blur_fast.hip)
 int km_blur_fast_supported(const void* x, const void* y, int H, int W, int kH, int kW, int border, int same, int dtype);
+int km_blur_fast_bwd_supported(const void* gy, const void* gx, int H, int W, int kH, int kW, int border, int same, int dtype);
 int km_blur_fast_run(bool bwd, const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk, int K,
                      int border, int dtype, hipStream_t s);
 static int km_sep_algo() {
@@ -638,7 +639,7 @@ int km_filter2d_sep_bwd_input(const void* gy, const void* kx, const void* ky, vo
     if (B == 0 || C == 0) return 0;  // empty batch
     if (km_filter_validate("km_filter2d_sep_bwd_input", B, C, H, W, Bk, kH, kW, border, same, dtype)) return -1;
     KM_REQUIRE(gy && kx && ky && gx, "km_filter2d_sep_bwd_input: null pointer");
-    if (km_sep_algo() == 0 && km_blur_fast_supported(gy, gx, H, W, kH, kW, border, same, dtype))
+    if (km_sep_algo() == 0 && km_blur_fast_bwd_supported(gy, gx, H, W, kH, kW, border, same, dtype))
         return km_blur_fast_run(true, gy, kx, ky, gx, B, C, H, W, Bk, kH, border, dtype, (hipStream_t)stream);
     KM_REQUIRE(kH - 1 <= KM_FS_TH && kW - 1 <= KM_FS_TW, "km_filter2d_sep_bwd_input: kernel larger than the tile; use the generic path");
     const KmFilterGeom g = km_filter_geom(B, C, H, W, Bk, kH, kW, border, same);
