@@ -245,7 +245,7 @@ def test_augmentation_hooks_with_probabilities_on_the_host_build():
             assert not hasattr(direct, "_kornia_amd_blended_with")
         finally:
             assert P.unpatch() == n
-    # one select pass only - the blur's (its switch cannot ride in the taps bit for bit, kornia_amd/augmentation.py); the warps and
+    # one select pass only - the blur's (its switch cannot ride in the taps bit for bit, kornia_amd/augmentation/functional.py); the warps and
     # the colour kernel carried theirs inside their own launches
     assert selects == [tuple(x.shape)], selects
     # the reference's own backward on the CPU for the same parameters
