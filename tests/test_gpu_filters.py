@@ -81,6 +81,123 @@ def test_filter2d_separable_kernel_grads_use_two_pass(oracle):
     assert kx.grad is not None and ky.grad is not None and torch.isfinite(kx.grad).all()
 
 
+# ---- small integers: every partial sum, in any order, is an integer below 2^24, so forward, input gradient and tap gradient must EQUAL
+# an fp64 F.pad + F.conv2d autograd reference (the tolerance tests around these keep non-integer data and the oracle's rounding order)
+def _ints(g, lo, hi, *shape):
+    return torch.randint(lo, hi + 1, shape, generator=g).float()
+
+
+def _conv64(x64, k64, border):
+    """filter2d in fp64 tensor operations: sample b is correlated with kernel b % Bk, padded (k-1)//2 before and the rest after"""
+    import torch.nn.functional as F
+
+    B, C, H, W = x64.shape
+    Bk, kH, kW = k64.shape
+    pl, pt = (kW - 1) // 2, (kH - 1) // 2
+    xp = F.pad(x64, (pl, kW - 1 - pl, pt, kH - 1 - pt), mode=border)
+    w = k64[torch.arange(B) % Bk][:, None].expand(B, C, kH, kW).reshape(B * C, 1, kH, kW)
+    return F.conv2d(xp.reshape(1, B * C, *xp.shape[-2:]), w, groups=B * C).view(B, C, H, W)
+
+
+def _filter2d_ref64(x, k, go, border):
+    x64, k64 = x.double().requires_grad_(), k.double().requires_grad_()
+    y = _conv64(x64, k64, border)
+    y.backward(go.double())
+    return y.detach(), x64.grad, k64.grad
+
+
+def _assert_filter2d_exact(x, k, go, border, dtype=torch.float32):
+    import kornia_amd as K
+
+    y64, gx64, gk64 = _filter2d_ref64(x, k, go, border)
+    assert max(y64.abs().max(), gx64.abs().max(), gk64.abs().max()).item() < 2 ** 24
+    xg, kg = x.to(dtype).cuda().requires_grad_(), k.to(dtype).cuda().requires_grad_()
+    y = K.filter2d(xg, kg, border)
+    y.backward(go.to(dtype).cuda())
+    assert y.dtype == dtype and xg.grad.dtype == dtype and kg.grad.dtype == dtype
+    assert torch.equal(y.detach().cpu(), y64.to(dtype)), f"forward: {(y.detach().cpu().double() - y64).abs().max().item()}"
+    assert torch.equal(xg.grad.cpu(), gx64.to(dtype)), f"input gradient: {(xg.grad.cpu().double() - gx64).abs().max().item()}"
+    assert torch.equal(kg.grad.cpu(), gk64.to(dtype)), f"tap gradient: {(kg.grad.cpu().double() - gk64).abs().max().item()}"
+    assert gk64.abs().max() > 0 and gx64.abs().max() > 0
+
+
+@pytest.mark.parametrize("shape,ks", [((2, 3, 37, 72), (3, 3)), ((2, 1, 70, 260), (5, 5)), ((2, 2, 33, 8), (7, 7)), ((2, 2, 19, 45), (3, 3)),
+                                      ((2, 2, 19, 45), (4, 3)), ((3, 1, 9, 14), (1, 7)), ((2, 2, 37, 72), (5, 6)),
+                                      ((4, 2, 20, 72), (5, 5)), ((4, 1, 11, 13), (3, 4))])
+@pytest.mark.parametrize("border", BORDERS)
+def test_filter2d_integer_data_is_exact(border, shape, ks):
+    """filter2d on integers in -3 .. 3: the register-tiled forward / adjoint / tap-gradient kernels (square odd 3 / 5 / 7 with W % 4 == 0,
+    a ragged 32-row strip, a second x tile at W = 260), the frame kernel and the generic kernels (even, rectangular, W % 4 != 0) equal
+    fp64 entry for entry, with one shared kernel, one per sample, and - B = 4 - two kernels used alternately."""
+    B = shape[0]
+    g = torch.Generator().manual_seed(31)
+    for Bk in ((2,) if B == 4 else (1, B)):
+        x, go, k = _ints(g, -3, 3, *shape), _ints(g, -3, 3, *shape), _ints(g, -3, 3, Bk, *ks)
+        _assert_filter2d_exact(x, k, go, border)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("shape", [(2, 3, 37, 72), (2, 2, 19, 45)])
+@pytest.mark.parametrize("border", BORDERS)
+def test_filter2d_integer_data_is_exact_in_16_bit(border, shape, dtype):
+    """3 x 3 on integers in -2 .. 2: outputs and input gradients are at most 36 in magnitude, exact in bf16 and f16; the tap gradient is an
+    exact integer in the fp64 accumulator and is rounded once, to the taps' dtype."""
+    g = torch.Generator().manual_seed(32)
+    for Bk in (1, shape[0]):
+        x, go, k = _ints(g, -2, 2, *shape), _ints(g, -2, 2, *shape), _ints(g, -2, 2, Bk, 3, 3)
+        _assert_filter2d_exact(x, k, go, border, dtype)
+
+
+@pytest.mark.parametrize("W", [64, 45])
+@pytest.mark.parametrize("K", [3, 5, 9, 11, 23])
+@pytest.mark.parametrize("border", BORDERS)
+def test_filter2d_separable_integer_data_is_exact(border, K, W):
+    """The fused separable filter and its adjoint on integers (x, grad_out in -3 .. 3, taps in -2 .. 2): register-tiled (W % 4 == 0, K <= 9),
+    LDS (W = 45) and large-kernel (K >= 10) paths equal the fp64 composition of the row pass and the column pass."""
+    import kornia_amd as K_
+
+    shape = (2, 2, 41, W)
+    g = torch.Generator().manual_seed(33)
+    for Bk in (1, 2):
+        x, go = _ints(g, -3, 3, *shape), _ints(g, -3, 3, *shape)
+        kx, ky = _ints(g, -2, 2, Bk, K), _ints(g, -2, 2, Bk, K)
+        x64 = x.double().requires_grad_()
+        y64 = _conv64(_conv64(x64, kx.double()[:, None, :], border), ky.double()[:, :, None], border)
+        y64.backward(go.double())
+        assert max(y64.abs().max(), x64.grad.abs().max()).item() < 2 ** 24 and x64.grad.abs().max() > 0
+        xg = x.cuda().requires_grad_()
+        y = K_.filter2d_separable(xg, kx.cuda(), ky.cuda(), border)
+        y.backward(go.cuda())
+        assert torch.equal(y.detach().cpu(), y64.detach().float()), f"forward: {(y.detach().cpu().double() - y64.detach()).abs().max().item()}"
+        assert torch.equal(xg.grad.cpu(), x64.grad.float()), f"input gradient: {(xg.grad.cpu().double() - x64.grad).abs().max().item()}"
+
+
+@pytest.mark.parametrize("kW,kH", [(5, 3), (3, 7), (9, 9)])
+@pytest.mark.parametrize("border", BORDERS)
+def test_filter2d_separable_kernel_grads_are_exact(border, kW, kH):
+    """Separable kernels that require grad (two filter2d passes): kx.grad and ky.grad - and the forward and the input gradient - equal fp64
+    on integer data."""
+    import kornia_amd as K_
+
+    shape = (2, 2, 19, 45)
+    g = torch.Generator().manual_seed(34)
+    for Bk in (1, 2):
+        x, go = _ints(g, -3, 3, *shape), _ints(g, -3, 3, *shape)
+        kx, ky = _ints(g, -2, 2, Bk, kW), _ints(g, -2, 2, Bk, kH)
+        x64, kx64, ky64 = x.double().requires_grad_(), kx.double().requires_grad_(), ky.double().requires_grad_()
+        y64 = _conv64(_conv64(x64, kx64[:, None, :], border), ky64[:, :, None], border)
+        y64.backward(go.double())
+        assert max(y64.abs().max(), x64.grad.abs().max(), kx64.grad.abs().max(), ky64.grad.abs().max()).item() < 2 ** 24
+        xg, kxg, kyg = x.cuda().requires_grad_(), kx.cuda().requires_grad_(), ky.cuda().requires_grad_()
+        y = K_.filter2d_separable(xg, kxg, kyg, border)
+        y.backward(go.cuda())
+        assert torch.equal(y.detach().cpu(), y64.detach().float())
+        assert torch.equal(xg.grad.cpu(), x64.grad.float())
+        assert torch.equal(kxg.grad.cpu(), kx64.grad.float()), f"kx.grad: {(kxg.grad.cpu().double() - kx64.grad).abs().max().item()}"
+        assert torch.equal(kyg.grad.cpu(), ky64.grad.float()), f"ky.grad: {(kyg.grad.cpu().double() - ky64.grad).abs().max().item()}"
+        assert kx64.grad.abs().max() > 0 and ky64.grad.abs().max() > 0
+
+
 @pytest.mark.parametrize("border", BORDERS)
 def test_gaussian_blur2d(oracle, border):
     import kornia_amd as K
@@ -273,6 +390,74 @@ def test_transform_points(oracle):
     assert K.transform_points(torch.eye(3)[None].cuda(), torch.zeros(1, 0, 2).cuda()).shape == (1, 0, 2)
     with pytest.raises(ValueError):
         K.transform_points(torch.eye(3)[None].expand(2, 3, 3).cuda(), torch.zeros(3, 4, 2).cuda())
+
+
+def _transform_points_expr(T, P):
+    """transform_points as tensor operations (pad with ones, multiply by T^T, scale = 1 / (w + 1e-8) where |w| > 1e-8, else 1)"""
+    h = torch.cat([P, torch.ones_like(P[..., :1])], -1) @ T.transpose(-1, -2)
+    w = h[..., -1:]
+    return torch.where(w.abs() > 1e-8, 1.0 / (w + 1e-8), torch.ones_like(w)) * h[..., :-1]
+
+
+def _transform_points_grads(fn, T, P, go, dtype):
+    Tg, Pg = T.detach().to(dtype).clone().requires_grad_(), P.detach().to(dtype).clone().requires_grad_()
+    fn(Tg, Pg).backward(go.to(dtype))
+    return Tg.grad.double().cpu(), Pg.grad.double().cpu()
+
+
+@pytest.mark.parametrize("n_pts", [1, 63, 64, 65, 255, 256, 257, 1000])
+@pytest.mark.parametrize("D", [2, 3])
+def test_transform_points_backward_fp32_against_fp64(D, n_pts):
+    """km_transform_points_bwd_kernel<float>: both gradients against fp64 autograd of the same expression, at point counts around one wave
+    (64) and one block (256: the 4-wave sum through LDS, the atomics of a batch's second and later blocks), with per-batch matrices and
+    a shared one (atomics of all batches into one matrix), and with points whose homogeneous coordinate is exactly zero (last row
+    (1, 0, ..) and x == 0: the |w| <= 1e-8 branch, scale 1 and no gradient through w).
+
+    Bound per gradient tensor: max |kernel - ref64| <= 2 (max |ref32 - ref64| + 2^-23 max |ref64|), ref32 being the same expression in fp32
+    evaluated here - the reference arithmetic's own error plus one rounding of the largest entry, times 2 for another rounding order of
+    the single terms (fma against multiply-add).  Worst measured ratio of the kernel's error to that bracket (without the 2): 0.85 on
+    the host build of the kernels (a CPU run), 0.86 on the MI355X."""
+    import kornia_amd as K
+
+    B = 3
+    g = torch.Generator().manual_seed(100 * D + n_pts)
+    T = torch.eye(D + 1)[None] + 0.1 * torch.randn(B, D + 1, D + 1, generator=g)
+    P = torch.rand(B, n_pts, D, generator=g) * 2 - 1
+    # homogeneous coordinate == x: exactly zero for a few points (at most 3, the first and the last one among them), 0.25 <= |x| <= 1 for the others
+    Tz = T.clone()
+    Tz[:, D] = 0.0
+    Tz[:, D, 0] = 1.0
+    Pz = P.clone()
+    Pz[..., 0] = torch.where(Pz[..., 0] < 0, -0.25 + 0.75 * Pz[..., 0], 0.25 + 0.75 * Pz[..., 0])
+    zero_at = sorted({0, n_pts // 2, n_pts - 1})
+    Pz[:, zero_at, 0] = 0.0
+    worst = 0.0
+
+    def check(what, got, want64, ref64, ref32):
+        """`got` against `want64` within the bracket of the reference arithmetic (ref32 against ref64)"""
+        nonlocal worst
+        bracket = (ref32 - ref64).abs().max().item() + 2.0 ** -23 * ref64.abs().max().item()
+        err = (got - want64).abs().max().item()
+        worst = max(worst, err / bracket)
+        print(f"transform_points bwd D={D} N={n_pts} {what}: err {err:.3e} bracket {bracket:.3e} ratio {err / bracket:.3f}")
+        assert ref64.abs().max() > 0 and got.abs().max() > 0, what
+        assert err <= 2 * bracket, (what, err, bracket)
+
+    for name, Tc, Pc in (("per-batch", T, P), ("shared", T[:1], P), ("w == 0 per-batch", Tz, Pz), ("w == 0 shared", Tz[:1], Pz)):
+        go = torch.randn(B, n_pts, D, generator=g)
+        gT64, gP64 = _transform_points_grads(_transform_points_expr, Tc, Pc, go, torch.float64)
+        gT32, gP32 = _transform_points_grads(_transform_points_expr, Tc, Pc, go, torch.float32)
+        gT, gP = _transform_points_grads(K.transform_points, Tc.cuda(), Pc.cuda(), go.cuda(), torch.float32)
+        check(name + " dT", gT, gT64, gT64, gT32)
+        check(name + " dP", gP, gP64, gP64, gP32)
+        if name.startswith("w == 0"):
+            w = (torch.cat([Pc, torch.ones_like(Pc[..., :1])], -1) @ Tc.transpose(-1, -2))[..., -1]
+            assert (w[:, zero_at] == 0).all() and (w.abs() >= 0.25).sum() == B * (n_pts - len(zero_at))  # the branch is taken, by these points only
+        if Tc.shape[0] == 1:
+            # one matrix for all batches = the sum over the batch of the per-batch run with B copies of it
+            gTb, _ = _transform_points_grads(K.transform_points, Tc.expand(B, -1, -1).contiguous().cuda(), Pc.cuda(), go.cuda(), torch.float32)
+            check(name + " dT == sum of per-batch dT", gT, gTb.sum(0, keepdim=True), gT64, gT32)
+    assert worst <= 2
 
 
 def test_filters_fp64_gradcheck():

@@ -144,3 +144,107 @@ def test_hysteresis_sweeps_follow_a_chain_across_tiles():
         assert sweeps < 200
     assert torch.equal(out.cpu(), want)
     assert 2 <= sweeps <= 2 + len(rows) * 4  # more than one sweep (the chain crosses tiles), far fewer than one per pixel of its length
+
+
+def _neighbour_code(gx, gy):
+    """the reference's direction bin of an integer gradient, 0 .. 7 (east, south-east, ... as in the kernel's table)"""
+    import math
+
+    return torch.round(torch.atan2(gy.double(), gx.double()) * (4 / math.pi)).long() % 8
+
+
+def test_nms_equals_the_reference_tail_exactly():
+    """km_canny_nms_fwd against the reference's own magnitude / direction / suppression / threshold code on prepared gradient planes
+    (tests/golden/canny_nms.npz, tests/make_golden_canny_nms.py): integers in -12 .. 12 over 32, so every product and sum is exact,
+    sqrt is correctly rounded on both sides and no direction sits within 2e-3 of a bin border - magnitude and edges must be EQUAL, with
+    eps = 0 and eps = 1e-6.  The fixture has plateaus (ties between a pixel and the neighbour it is compared with, which the strict
+    `> 0` must suppress), magnitudes exactly on both thresholds (which the strict `>` must not count) and every one of the 8
+    directions; (37, 130) leaves a 2-column last tile, a 5-row last block and a part-filled group of 4 rows."""
+    from kornia_amd import _native as N
+
+    d = golden("canny_nms")
+    p = d["planes"].long()
+    B, _, H, W = p.shape
+    scale, low, high = int(d["scale"]), float(d["low"]), float(d["high"])
+    assert (B, H, W) == (2, 37, 130) and d["eps"].tolist() == [0.0, 1e-6]
+    # the fixture still exercises what it is for (conditions on the input)
+    gx, gy = p[:, 0], p[:, 1]
+    code = _neighbour_code(gx, gy)
+    for k in range(8):
+        assert (code == k).float().mean().item() >= 0.05, k
+    m2 = torch.nn.functional.pad(gx * gx + gy * gy, (1, 1, 1, 1), value=-1)  # squared magnitude in units of 1 / scale^2: equal iff the magnitudes are
+    dy = torch.tensor([0, 1, 1, 1, 0, -1, -1, -1])[code]
+    dx = torch.tensor([1, 1, 0, -1, -1, -1, 0, 1])[code]
+    bb, ii, jj = torch.meshgrid(torch.arange(B), torch.arange(H), torch.arange(W), indexing="ij")
+    centre = m2[bb, ii + 1, jj + 1]
+    ties = (m2[bb, ii + 1 + dy, jj + 1 + dx] == centre) | (m2[bb, ii + 1 - dy, jj + 1 - dx] == centre)
+    assert ties.sum().item() >= 200
+    kept0 = d["mag_eps0"][d["mag_eps0"] > 0]
+    assert ((kept0 == low) | (kept0 == high)).sum().item() >= 20
+
+    lib = N.lib()
+    grads = (p.float() / scale).cuda().contiguous()  # (B,2,H,W)
+    for n, eps in enumerate(d["eps"].tolist()):
+        mag = torch.full((B, H, W), -1.0, device="cuda")
+        edges = torch.full((B, H, W), -1.0, device="cuda")
+        N.check(lib.km_canny_nms_fwd(grads.data_ptr(), mag.data_ptr(), edges.data_ptr(), B, H, W, low, high, eps, N.stream_ptr(grads.device)), "nms")
+        want_mag, want_edges = d[f"mag_eps{n}"][:, 0], d[f"edges2_eps{n}"][:, 0].float() / 2
+        assert torch.equal(mag.cpu(), want_mag), f"eps={eps}: {(mag.cpu() != want_mag).sum().item()} magnitudes differ"
+        assert torch.equal(edges.cpu(), want_edges), f"eps={eps}: {(edges.cpu() != want_edges).sum().item()} edge pixels differ"
+
+
+def _hysteresis_fixed_point(state):
+    """the reference's loop (kornia/filters/canny.py:146-159) on the host: (edges after it, the number of passes it took, the last one included)"""
+    ref, passes = state.clone(), 0
+    while True:
+        grown = torch.nn.functional.max_pool2d((ref == 1).float(), 3, 1, 1) > 0
+        new = torch.where((ref == 0.5) & grown, torch.ones_like(ref), ref)
+        passes += 1
+        if torch.equal(new, ref):
+            return (ref == 1).float(), passes
+        ref = new
+
+
+def test_hysteresis_sweeps_at_tile_corners_image_borders_and_between_images():
+    """km_canny_hysteresis_sweep where an index slip shows and the serpentine above does not go: a diagonal neighbour across a tile
+    corner, the last row of one image against the first row of the next (adjacent in memory, in both roles), the end of a row against
+    the start of the next, a weak run that crosses the x = 64 tile border with its seed beyond it, the image corner, and isolated weak
+    pixels; then a random state (30 % weak, 3 % strong).  Equal to the reference's loop; a sweep does at least what one pass of that
+    loop does, so it needs no more sweeps than the loop needs passes."""
+    from kornia_amd import _native as N
+
+    lib = N.lib()
+    B, H, W = 2, 70, 130
+    hand = torch.zeros(B, 1, H, W)
+    hand[0, 0, 63, 63], hand[0, 0, 64, 64] = 0.5, 1.0                # diagonal across the corner of four tiles
+    hand[0, 0, H - 1, 10:20], hand[1, 0, 0, 10:20] = 0.5, 1.0        # weak "above" strong across two images: not neighbours
+    hand[0, 0, H - 1, 30:40], hand[1, 0, 0, 30:40] = 1.0, 0.5        # and the roles exchanged
+    hand[0, 0, 5, W - 1], hand[0, 0, 6, 0] = 1.0, 0.5                # the row wrap: not neighbours
+    hand[0, 0, 20, 50:81], hand[0, 0, 21, 80] = 0.5, 1.0             # a run across x = 64, seeded below its far end
+    hand[1, 0, H - 1, W - 1], hand[1, 0, H - 2, W - 2] = 0.5, 1.0    # the image corner
+    for b, i, j in ((0, 40, 100), (1, 30, 64), (1, 63, 0), (0, 0, 0), (1, 64, 63)):
+        hand[b, 0, i, j] = 0.5                                       # isolated weak pixels
+    g = torch.Generator().manual_seed(11)
+    u = torch.rand(B, 1, H, W, generator=g)
+    rand = torch.where(u < 0.03, torch.ones_like(u), torch.where(u < 0.33, torch.full_like(u, 0.5), torch.zeros_like(u)))
+    for name, state in (("hand", hand), ("random", rand)):
+        want, passes = _hysteresis_fixed_point(state)
+        if name == "hand":
+            assert want[0, 0, 63, 63] == 1 and want[0, 0, 20, 50:81].all() and want[1, 0, H - 1, W - 1] == 1
+            assert want[0, 0, H - 1, 10:20].sum() == 0 and want[1, 0, 0, 30:40].sum() == 0 and want[0, 0, 6, 0] == 0
+            assert want.sum() == (state == 1).sum() + 1 + 31 + 1  # nothing else is promoted
+        else:
+            assert want.sum() > (state == 1).sum() + 100 and ((state == 0.5) & (want == 0)).sum() > 100
+        st = state.cuda().contiguous()
+        out = torch.full_like(st, -1.0)
+        flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+        sweeps = 0
+        while True:
+            N.check(lib.km_canny_hysteresis_sweep(st.data_ptr(), out.data_ptr(), flag.data_ptr(), B, H, W, N.stream_ptr(st.device)), "sweep")
+            sweeps += 1
+            if int(flag.item()) == 0:
+                break
+            flag.zero_()
+            assert sweeps < 200
+        assert torch.equal(out.cpu(), want), f"{name}: {(out.cpu() != want).sum().item()} pixels differ"
+        assert 2 <= sweeps <= passes, (name, sweeps, passes)
