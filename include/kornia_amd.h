@@ -32,7 +32,8 @@
  *   bit of `km_abi_features()`.  That symbol is itself new, so a binding looks it up with dlsym and treats its absence as 0.
  *     bit 0  km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd (masks, RandomPerspective and inverse() of the
  *            augmentation container);
- *     bit 1  km_crop_resize_fwd (crop_by_indices, RandomResizedCrop and the random flips).
+ *     bit 1  km_crop_resize_fwd (crop_by_indices, RandomResizedCrop and the random flips);
+ *     bit 2  km_median_blur_supported, km_median_blur_fwd, km_median_blur_bwd (median_blur, MedianBlur, RandomMedianBlur).
  */
 #ifndef KORNIA_AMD_H
 #define KORNIA_AMD_H
@@ -370,6 +371,24 @@ int km_color_jitter_bwd(const void* x, const void* gy, void* gx, const void* par
                         const void* enable, const void* apply, const int* stages, int n_stages, int B, int H, int W, int dtype, void* stream);
 int km_select_samples_fwd(const void* transformed, const void* original, const void* apply, void* out, int B,
                           long long n_per_sample, int dtype, void* stream);
+
+/* ---- median_blur (km_abi_features() bit 2) -----------------------------------------------------
+ * Replaces kornia/filters/median.py:35-72 (get_binary_kernel2d + F.conv2d into a (B C, ky kx, H, W) copy of the image + torch.median) and,
+ * with `apply`, RandomMedianBlur (kornia/augmentation/_2d/intensity/median_blur.py:59-68) with its probability blend.  One pass:
+ * x (B,C,H,W) dtype -> y (B,C,H,W) dtype, zero padding by (ky / 2, kx / 2), the window's element of rank (ky kx - 1) / 2; bit-identical to
+ * the reference in every dtype.  For ky kx >= 2 an output is NaN exactly when its window holds a NaN or +-inf of the image; 1 x 1 is the
+ * identity.  ky, kx odd, 1 .. 15 (km_median_blur_supported: 1 when the window and dtype are taken, else 0 - the entry points then return < 0).
+ *   idx    (B,C,H,W) uint8, nullable: the window position p kx + q that supplied each median - among equal values the smallest one (the
+ *          reference leaves the choice to ATen's sort); at a NaN output unspecified but < ky kx.  Written only when given.
+ *   apply  (B) fp32, nullable: a sample with apply <= 0.5 (or NaN) is copied through in the same launch (its idx is not written).
+ * km_median_blur_bwd: gx (B,C,H,W) dtype = the gather of gy (B,C,H,W) dtype through the forward's idx - no atomics, fp32 (f64: fp64)
+ * accumulation in row-major window order, one rounding; gradient routed to the padding is dropped; samples the forward copied (the same
+ * `apply`) pass gy through. */
+int km_median_blur_supported(int ky, int kx, int dtype);
+int km_median_blur_fwd(const void* x, void* y, void* idx, const void* apply, int B, int C, int H, int W, int ky, int kx, int dtype,
+                       void* stream);
+int km_median_blur_bwd(const void* gy, const void* idx, const void* apply, void* gx, int B, int C, int H, int W, int ky, int kx, int dtype,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,11 +12,13 @@ from . import augmentation, core, enhance, filters, geometry, graph
 from ._native import NativeLibraryError, is_built, library_path
 from .filters import (
     GaussianBlur2d,
+    MedianBlur,
     Sobel,
     SpatialGradient,
     filter2d,
     filter2d_separable,
     gaussian_blur2d,
+    median_blur,
     sobel,
     spatial_gradient,
 )

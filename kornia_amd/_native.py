@@ -77,9 +77,14 @@ _PROTOTYPES = {
     "km_inverse_chain_fwd": [_P, _I, _P, _I, _I, _I, _P],
     # km_abi_features() bit 1
     "km_crop_resize_fwd": [_P] * 7 + [_I] * 13 + [_P],
+    # km_abi_features() bit 2
+    "km_median_blur_supported": [_I, _I, _I],
+    "km_median_blur_fwd": [_P] * 4 + [_I] * 7 + [_P],
+    "km_median_blur_bwd": [_P] * 4 + [_I] * 7 + [_P],
 }
-ABI_FEATURES = 3  # the km_abi_features() bits this binding calls
-_FEATURE_SYMBOLS = {"km_warp2d_pair_fwd": 1, "km_perspective_params_chain_fwd": 1, "km_inverse_chain_fwd": 1, "km_crop_resize_fwd": 2}
+ABI_FEATURES = 7  # the km_abi_features() bits this binding calls
+_FEATURE_SYMBOLS = {"km_warp2d_pair_fwd": 1, "km_perspective_params_chain_fwd": 1, "km_inverse_chain_fwd": 1, "km_crop_resize_fwd": 2,
+                    "km_median_blur_supported": 4, "km_median_blur_fwd": 4, "km_median_blur_bwd": 4}
 KM_MASK_CODES = {torch.bool: 0, torch.uint8: 1, torch.int32: 2, torch.int64: 3, torch.float32: 4, torch.bfloat16: 5, torch.float16: 6}
 
 _lib: Optional[ctypes.CDLL] = None

@@ -10,9 +10,9 @@ from .container import AugmentationSequential, ParamItem
 from .crop_flip import RandomHorizontalFlip, RandomResizedCrop, RandomVerticalFlip
 from .functional import (affine_chain, affine_matrix, apply_sequence, color_jitter, gaussian_taps, inverse_chain, perspective_chain, random_affine,
                          random_gaussian_blur, random_perspective, select_samples, warp_pair)
-from .modules import ColorJitter, RandomAffine, RandomGaussianBlur, RandomPerspective
+from .modules import ColorJitter, RandomAffine, RandomGaussianBlur, RandomMedianBlur, RandomPerspective
 
-__all__ = ["AugmentationSequential", "ColorJitter", "ParamItem", "RandomAffine", "RandomGaussianBlur", "RandomHorizontalFlip", "RandomPerspective",
+__all__ = ["AugmentationSequential", "ColorJitter", "ParamItem", "RandomAffine", "RandomGaussianBlur", "RandomHorizontalFlip", "RandomMedianBlur", "RandomPerspective",
            "RandomResizedCrop", "RandomVerticalFlip", "affine_chain", "affine_matrix",
            "apply_sequence", "color_jitter", "gaussian_taps", "inverse_chain", "perspective_chain", "random_affine", "random_gaussian_blur",
            "random_perspective", "select_samples", "warp_pair"]

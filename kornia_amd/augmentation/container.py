@@ -40,7 +40,7 @@ class AugmentationSequential(torch.nn.Module):
         for i, m in enumerate(args):
             if not isinstance(m, _RandomOp):
                 raise NotImplementedError(f"child {i} ({type(m).__name__}) is not one of this package's modules (RandomAffine, RandomPerspective, "
-                                          "RandomResizedCrop, RandomHorizontalFlip, RandomVerticalFlip, ColorJitter, RandomGaussianBlur)")
+                                          "RandomResizedCrop, RandomHorizontalFlip, RandomVerticalFlip, ColorJitter, RandomGaussianBlur, RandomMedianBlur)")
             if same_on_batch is not None:
                 m.same_on_batch = bool(same_on_batch)
             if keepdim is not None:

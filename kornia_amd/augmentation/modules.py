@@ -18,7 +18,7 @@ Beyond config 3: RandomPerspective, label masks in the container (``data_keys`` 
 dictionaries, lists of masks and ``random_apply`` still raise.  RandomResizedCrop and the two random flips run on the batched crop kernel
 (``km_crop_resize_fwd``); flips right after a slice-mode crop ride in its launch, and children after a crop sample at its size.
 
-This file holds the matrix-chain family (RandomAffine, RandomPerspective) and the two intensity modules; what every module shares is in
+This file holds the matrix-chain family (RandomAffine, RandomPerspective) and the three intensity modules; what every module shares is in
 :mod:`.base`, the crop / flip family in :mod:`.crop_flip`, the container in :mod:`.container`.
 """
 from __future__ import annotations
@@ -29,7 +29,7 @@ import torch
 
 from .base import _GeometricOp, _RandomOp, fan_out
 from .draws import _Draws, _range_pair
-from .functional import (NATIVE_DTYPES, _kernel_hw, affine_chain, color_jitter, inverse_chain, perspective_chain, random_affine,
+from .functional import (NATIVE_DTYPES, _kernel_hw, _prob, affine_chain, color_jitter, inverse_chain, perspective_chain, random_affine,
                          random_gaussian_blur, random_perspective, warp_pair)
 
 
@@ -305,3 +305,20 @@ class RandomGaussianBlur(_RandomOp):
 
     def _apply(self, x: torch.Tensor, params: dict) -> torch.Tensor:
         return random_gaussian_blur(x, params, self.kernel_size, self.border_type, self.separable)
+
+
+class RandomMedianBlur(_RandomOp):
+    """``kornia.augmentation.RandomMedianBlur`` (kornia/augmentation/_2d/intensity/median_blur.py:26-68): it draws ``batch_prob`` only; the
+    median filter and the per-sample switch are ONE launch (``km_median_blur_fwd`` copies the samples whose draw failed), differentiable."""
+
+    def __init__(self, kernel_size=(3, 3), same_on_batch: bool = False, p: float = 0.5, keepdim: bool = False) -> None:
+        super().__init__(p, same_on_batch, keepdim)
+        self.kernel_size = _kernel_hw(kernel_size)
+
+    def _sample(self, d: _Draws, shape, params: dict) -> None:
+        pass  # (no parameter beyond the probability draw)
+
+    def _apply(self, x: torch.Tensor, params: dict) -> torch.Tensor:
+        from ..filters.median import _median_blur
+
+        return _median_blur(x, self.kernel_size, _prob(params, x.device, x.shape[0]))

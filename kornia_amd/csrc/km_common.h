@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define KM_ABI_FEATURES 3  // km_abi_features(): bit 0 = km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd; bit 1 = km_crop_resize_fwd
+#define KM_ABI_FEATURES 7  // km_abi_features(): bit 0 = km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd; bit 1 = km_crop_resize_fwd; bit 2 = km_median_blur_supported / _fwd / _bwd
 #define KM_ABI_VERSION 3  // include/kornia_amd.h, "Versioning": a library of version N exports the symbol sets of every version <= N
 
 // dtype codes of the C ABI (include/kornia_amd.h)
@@ -322,6 +322,19 @@ __device__ __forceinline__ float km_fmod(float a, float b) { return fmodf(a, b);
 __device__ __forceinline__ double km_fmod(double a, double b) { return fmod(a, b); }
 __device__ __forceinline__ float km_sqrt(float x) { return __builtin_sqrtf(x); }  // IEEE (built with -fhip-fp32-correctly-rounded-divide-sqrt)
 __device__ __forceinline__ double km_sqrt(double x) { return __builtin_sqrt(x); }
+
+// Three-operand minimum / maximum / median (v_min3_f32, v_max3_f32, v_med3_f32: one VALU instruction each - the nested two-operand
+// forms are what the gfx950 back end folds into the first two, the third has a builtin).  The host pass, and the host build of the
+// kernels, compose them from fminf / fmaxf.  Operands are finite wherever the result is used (km_median.hip overwrites the rest).
+__device__ __forceinline__ float km_min3(float a, float b, float c) { return fminf(fminf(a, b), c); }
+__device__ __forceinline__ float km_max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+__device__ __forceinline__ float km_med3(float a, float b, float c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_fmed3f(a, b, c);
+#else
+    return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c));
+#endif
+}
 
 // fp32/fp64 global atomic add without return value (hardware global_atomic_add_f32/_f64 on gfx950)
 __device__ __forceinline__ void km_atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }

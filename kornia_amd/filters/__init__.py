@@ -20,6 +20,7 @@ from .kernels import (
     get_spatial_gradient_kernel2d,
     normalize_kernel2d,
 )
+from .median import MedianBlur, median_blur
 from .sobel import Sobel, SpatialGradient, sobel, spatial_gradient
 
 # reference aliases (kornia/filters/filter.py:460-548)

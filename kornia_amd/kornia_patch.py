@@ -44,6 +44,8 @@ _NATIVE = {
     # blur + Sobel were already native through the two entries above; this one also replaces the ~25 elementwise / fixed-kernel
     # convolution launches and the host-synchronised hysteresis loop behind them (km_canny_nms_fwd, km_canny_hysteresis_sweep)
     "kornia.filters.canny": {"canny": _f.canny},
+    # one launch instead of the one-hot conv2d copy + torch.median; windows or dtypes the native op refuses stay on Kornia's own function
+    "kornia.filters.median": {"median_blur": _f.median_blur},
     # fused colour kernels (the ColorJitter leg)
     "kornia.enhance.adjust": {
         "adjust_brightness_accumulative": _e.adjust_brightness_accumulative,
@@ -78,8 +80,20 @@ def _use_native_color(args, kwargs) -> bool:
     return True
 
 
+def _use_native_median(args, kwargs) -> bool:
+    """median_blur: a 4-D image and a window the native op takes (odd sides up to 15); anything else - a 17 x 17 window, an even size
+    (Kornia's own error) - falls through to Kornia's function."""
+    from .filters.median import supported
+
+    if not _use_native(args, kwargs):
+        return False
+    image = args[0] if args else kwargs.get("input")
+    kernel_size = args[1] if len(args) > 1 else kwargs.get("kernel_size")
+    return isinstance(image, torch.Tensor) and image.dim() == 4 and supported(kernel_size, image.dtype)
+
+
 def _dispatcher(original: Callable, native: Callable) -> Callable:
-    accept = _use_native_color if id(native) in _COLOR_OPS else _use_native
+    accept = _use_native_color if id(native) in _COLOR_OPS else (_use_native_median if native is _f.median_blur else _use_native)
 
     @functools.wraps(original)
     def wrapper(*args, **kwargs):
