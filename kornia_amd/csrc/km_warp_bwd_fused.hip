@@ -484,7 +484,8 @@ __device__ __forceinline__ void kmo_pix(const KmtPix& q, const float (&go)[CC], 
     }
     // scale = 2^k: (wx * wy) * scale == wx * (wy * scale) bit for bit.  Tap-outer order: one exec-mask region per tap (the four taps
     // without exec-mask regions - zero weights, non-owned taps parked on a cell of the lane's own - and a wave-uniform skip of pixels that
-    // own no tap measured the same time: profiles/r04/bwd_fused_per_pixel_variants.txt).
+    // own no tap measured the same time: profiles/r04/bwd_fused_per_pixel_variants.txt.  That was the linear walk, where a whole wave rarely
+    // owned nothing; waves without a VALID lane - the column walk has them in every box's last slab - never get here: kmo_process).
     const float wy0s = FIXED ? t.wy0 * scale : t.wy0, wy1s = FIXED ? t.wy1 * scale : t.wy1;
     const float w00 = t.wx1 * wy1s, w01 = t.wx0 * wy1s, w10 = t.wx1 * wy0s, w11 = t.wx0 * wy0s;
     float gix = 0.f, giy = 0.f;
@@ -643,7 +644,10 @@ __device__ __forceinline__ void kmo_walk_none(KmoWalk& wk) {  // nothing to requ
 }
 // request slot s of the walk's tile (zeros beyond the end of the box) and advance
 template <typename T, int CC>
-__device__ __forceinline__ void kmo_request_slot(const T* const (&gout_c)[CC], int w, int s, KmoWalk& wk, float (&Gs)[CC]) {
+__device__ __forceinline__ void kmo_request_slot(const T* gout_b, size_t dst_plane, int w, int s, KmoWalk& wk, float (&Gs)[CC]) {
+    const T* gout_c[CC];  // (one base and the plane size are kept; the channels' pointers are formed at the request)
+#pragma unroll
+    for (int c = 0; c < CC; ++c) gout_c[c] = gout_b + (size_t)c * dst_plane;
 #if KMO_WALK_COLS
     (void)w;
     const bool valid = wk.trow < wk.nrows - s * wk.P;
@@ -665,7 +669,7 @@ __device__ __forceinline__ void kmo_request_slot(const T* const (&gout_c)[CC], i
 template <typename T, int CM, int ALIGN, int CC, bool FAST, bool FIXED, int PADX>
 __device__ __forceinline__ void kmo_process(const float (&m)[9], const KmoTile& d, const KmoConsts& k, float (&G)[KMO_SLOTS][CC], const float4* s_u4,
                                             const float4* s_v4, int* s_acc, const float* s_src, float scale, float (&A)[9], int w, KmoWalk& wn,
-                                            const T* const (&gout_n)[CC], bool mine, const KmWarpFusedArgs<T>& a, const KmoTile& nxt,
+                                            const T* gout_n, size_t dst_plane, bool mine, const KmWarpFusedArgs<T>& a, const KmoTile& nxt,
                                             float (&S)[CC * KMO_PLANE / KMO_NT], float* s_src_next) {
     const int tid = threadIdx.x;
     const int bw = max(d.bw, 1);
@@ -682,11 +686,16 @@ __device__ __forceinline__ void kmo_process(const float (&m)[9], const KmoTile& 
     for (int s = 0; s < KMO_SLOTS; ++s) {
         if (mine && s * P < nrows && !(KMO_ABL & 4)) {  // block-uniform
             const bool valid = trow < nrows - s * P;
-            const float4 r0 = s_v4[valid ? rbase + s * P : 0];
-            KmtPix q;
-            float gdx, gdy;
-            kmt_pix_position_pad<CM, ALIGN, FAST, PADX>(m, kmt_half(c0), kmt_half(r0), valid, k.Wm1, k.hW, k.Hm1, k.hH, (uint32_t)d.X0, (uint32_t)d.Y0, a.g.W, a.g.H, q, gdx, gdy);
-            kmo_pix<CM, CC, FAST, FIXED>(q, G[s], s_acc, s_src, scale, (uint32_t)d.TWc, (uint32_t)d.THc, c0.w, r0.w, PADX ? k.mx * gdx : k.mx, PADX ? k.my * gdy : k.my, A);
+            // A wave without a valid lane (the waves below the box's last row in its last slab: 9 of 16 in the fifth slab of a 66-row box) would
+            // own no tap and add nine zeros to A - finite partials that start at +0 stay what they are - after the table read, both divisions,
+            // the weights and kmg_terms: ~65 of a slot's ~110 vector instructions (profiles/r08_bwd_issue_slots.txt).  Wave-uniform; the refill below happens for every wave.
+            if (__ballot(valid) != 0ull) {
+                const float4 r0 = s_v4[valid ? rbase + s * P : 0];
+                KmtPix q;
+                float gdx, gdy;
+                kmt_pix_position_pad<CM, ALIGN, FAST, PADX>(m, kmt_half(c0), kmt_half(r0), valid, k.Wm1, k.hW, k.Hm1, k.hH, (uint32_t)d.X0, (uint32_t)d.Y0, a.g.W, a.g.H, q, gdx, gdy);
+                kmo_pix<CM, CC, FAST, FIXED>(q, G[s], s_acc, s_src, scale, (uint32_t)d.TWc, (uint32_t)d.THc, c0.w, r0.w, PADX ? k.mx * gdx : k.mx, PADX ? k.my * gdy : k.my, A);
+            }
         }
 #else
     const int di = d.di, dj = d.dj;
@@ -722,16 +731,18 @@ __device__ __forceinline__ void kmo_process(const float (&m)[9], const KmoTile& 
             const int vqi = valid ? qi : 0, vqj = valid ? qj : 0;
             const float4 c0 = s_u4[vqj], r0 = s_v4[vqi];
 #endif
-            KmtPix q;
-            float gdx, gdy;
-            kmt_pix_position_pad<CM, ALIGN, FAST, PADX>(m, kmt_half(c0), kmt_half(r0), valid, k.Wm1, k.hW, k.Hm1, k.hH, (uint32_t)d.X0, (uint32_t)d.Y0, a.g.W, a.g.H, q, gdx, gdy);
-            kmo_pix<CM, CC, FAST, FIXED>(q, G[s], s_acc, s_src, scale, (uint32_t)d.TWc, (uint32_t)d.THc, c0.w, r0.w, PADX ? k.mx * gdx : k.mx, PADX ? k.my * gdy : k.my, A);
+            if (__ballot(valid) != 0ull) {  // (wave-uniform: the waves beyond the end of the list, see the column walk)
+                KmtPix q;
+                float gdx, gdy;
+                kmt_pix_position_pad<CM, ALIGN, FAST, PADX>(m, kmt_half(c0), kmt_half(r0), valid, k.Wm1, k.hW, k.Hm1, k.hH, (uint32_t)d.X0, (uint32_t)d.Y0, a.g.W, a.g.H, q, gdx, gdy);
+                kmo_pix<CM, CC, FAST, FIXED>(q, G[s], s_acc, s_src, scale, (uint32_t)d.TWc, (uint32_t)d.THc, c0.w, r0.w, PADX ? k.mx * gdx : k.mx, PADX ? k.my * gdy : k.my, A);
+            }
 #if !KMO_TAB_AHEAD
             kmt_advance(qi, qj, di, dj, bw);
 #endif
         }
 #endif
-        kmo_request_slot<T, CC>(gout_n, w, s, wn, G[s]);
+        kmo_request_slot<T, CC>(gout_n, dst_plane, w, s, wn, G[s]);
         // the next tile's source tile is requested here, not before the loop: registers that are live across the whole loop get
         // moved by the register allocator at its entry, and a move of a register with a load in flight is a wait for that load
         if (s == KMO_SRC_AT && nxt.t >= 0 && nxt.regular && nxt.p == 0) {
@@ -1086,21 +1097,18 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
 #pragma unroll
     for (int k = 0; k < CC * KMO_PLANE / KMO_NT; ++k) S[k] = 0.f;
     {
-        const T* gout_c[CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) gout_c[c] = a.gout;
+        const T* gout_c = a.gout;
         KmoWalk w0;
         kmo_walk_init(a, cur, w0);
         if (cur.t >= 0 && cur.regular) {
-#pragma unroll
-            for (int c = 0; c < CC; ++c) gout_c[c] = a.gout + ((size_t)cur.plane0 + (size_t)c) * dst_plane;
+            gout_c = a.gout + (size_t)cur.plane0 * dst_plane;
             if constexpr (DMA) kmo_dma_src<T, CC>(a, cur, l.s_src);  // (tile q uses source buffer q & 1)
             else kmo_issue_src<T, CC>(a, cur, S);
         } else {
             kmo_walk_none(w0);
         }
 #pragma unroll
-        for (int s = 0; s < KMO_SLOTS; ++s) kmo_request_slot<T, CC>(gout_c, g.w, s, w0, G[s]);
+        for (int s = 0; s < KMO_SLOTS; ++s) kmo_request_slot<T, CC>(gout_c, dst_plane, g.w, s, w0, G[s]);
     }
     float A[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int pending_b = -1;      // row of gmat whose matrix-gradient partials sit in s_gm
@@ -1156,14 +1164,11 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
             nxt.p = cur.p + 1;
         }
         KMO_T(11)  // description: the next tile's fields
-        const T* gout_n[CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) gout_n[c] = a.gout;
+        const T* gout_n = a.gout;
         KmoWalk wn;
         kmo_walk_init(a, nxt, wn);
         if (nxt.t >= 0 && nxt.regular) {
-#pragma unroll
-            for (int c = 0; c < CC; ++c) gout_n[c] = a.gout + ((size_t)nxt.plane0 + (size_t)c) * dst_plane;
+            gout_n = a.gout + (size_t)nxt.plane0 * dst_plane;
         } else {
             kmo_walk_none(wn);  // (the end of the sequence, or a tile of the general launch: nothing to request)
         }
@@ -1215,7 +1220,7 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
         {
             float m[9];
             kmo_matrix(kmo_ring(l.s_box, q), m);
-            kmo_process<T, CM, ALIGN, CC, true, true, PADX>(m, cur, kc, G, l.s_u4, l.s_v4, l.s_acc, s_src_cur, scale, A, g.w, wn, gout_n, mine, a, nxt, S, s_src_nxt);
+            kmo_process<T, CM, ALIGN, CC, true, true, PADX>(m, cur, kc, G, l.s_u4, l.s_v4, l.s_acc, s_src_cur, scale, A, g.w, wn, gout_n, dst_plane, mine, a, nxt, S, s_src_nxt);
         }
         KMO_T(5)  // scatter
         if (!(KMO_ABL & 64)) KM_LDS_BARRIER();  // B2: every contribution of the pass is in the accumulators; the tables, s_red and (last pass) the source tile are free
