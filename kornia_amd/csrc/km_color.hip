@@ -28,7 +28,21 @@ struct KmColorArgs {
     uint32_t blocks_per_image, nblocks;
 };
 
-__device__ __forceinline__ float kmc_clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+// torch.clamp keeps a NaN; fminf / fmaxf return their other operand, so the NaN is put back (one compare and one select on top of the
+// min / max): a NaN pixel stays a NaN through every stage, as in the reference, instead of coming out as 0.
+__device__ __forceinline__ float kmc_sat01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }  // NaN -> 0: for values that cannot be NaN
+__device__ __forceinline__ float kmc_clamp01(float v) {
+    const float c = kmc_sat01(v);
+    return (v != v) ? v : c;
+}
+template <bool EXACT>
+__device__ __forceinline__ float kmc_clamp(float v) { return EXACT ? kmc_clamp01(v) : kmc_sat01(v); }
+// amax / amin over the channels as torch computes them: NaN if any channel is
+__device__ __forceinline__ void kmc_max_min(float r, float g, float b, float& mx, float& mn) {
+    mx = fmaxf(r, fmaxf(g, b));
+    mn = fminf(r, fminf(g, b));
+    if (__builtin_isunordered(r, g) || (b != b)) mx = mn = __builtin_nanf("");
+}
 __device__ __forceinline__ float kmc_gray(float r, float g, float b) {
     // r * w_r, then addcmul twice (color/gray.py:86-89)
     float o = r * 0.299f;
@@ -49,10 +63,13 @@ __device__ __forceinline__ float kmc_pymod(float a, float b) {
     return (r != 0.0f && r < 0.0f) ? r + b : r;
 }
 
+// EXACT: the channel maximum / minimum propagate a NaN (kmc_max_min); without it they are fmaxf / fminf, for the waves that passed the vote (KMC_TAME_MASK32)
+template <bool EXACT = true>
 __device__ __forceinline__ void kmc_hue(float& r, float& g, float& b, float shift) {
     const float two_pi = 6.283185307179586f;
     // rgb_to_hsv (color/hsv.py:54-75)
-    const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
+    float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
+    if (EXACT) kmc_max_min(r, g, b, mx, mn);
     float deltac = mx - mn;
     const float v = mx;
     const float s = deltac / (mx + 1e-8f);
@@ -98,7 +115,23 @@ __device__ __forceinline__ float kmc_rcp(float v) {
     return 1.0f / v;
 #endif
 }
+// A NaN or an infinite channel: in the reference's sequence the hue is then NaN whichever channel it is (an inf - inf or an inf / inf on
+// every branch of rgb_to_hsv), so hsv_to_rgb's sextant index is 0 and f is NaN, and the pixel comes out as (v, t, p) = (v, NaN, v (1 - s))
+// with v = amax and s = (amax - amin) / (amax + 1e-8).  The branch-free algebra below gives other patterns for such a pixel (v s is NaN
+// where s alone is not), so under EXACT that pixel is a special case: it takes the three values the reference's sequence was recorded to end in
+// (they rest on ATen's CPU cast of a NaN hue to sextant 0; tests/golden/nonfinite_pixels.npz pins them).
+// (A NaN hue SHIFT - a NaN factor with finite pixels - is not covered: kmc_sat01 of m below returns 0 for it, so the pixel comes out finite here,
+// as before; the record is of non-finite pixels.)
+template <bool EXACT = true>
 __device__ __forceinline__ void kmc_hue_fast(float& r, float& g, float& b, float shift) {
+    const float z = EXACT ? km_fma(b, 0.0f, km_fma(g, 0.0f, r * 0.0f)) : 0.0f;  // 0 if all three are finite, else NaN
+    if (EXACT && z != z) {
+        float mx, mn;
+        kmc_max_min(r, g, b, mx, mn);
+        const float s = (mx - mn) / (mx + 1e-8f);
+        r = mx; g = __builtin_nanf(""); b = mx * (1.0f - s);
+        return;
+    }
     const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
     const float delta = mx - mn, v = mx;
     const float vs = v * (delta * kmc_rcp(mx + 1e-8f));             // v * s
@@ -109,29 +142,56 @@ __device__ __forceinline__ void kmc_hue_fast(float& r, float& g, float& b, float
     ht = ht - floorf(ht);                                              // [0, 1)
     h6 = ht * 6.0f;
     float k, m;
-    k = h6 + 5.0f; k = k >= 6.0f ? k - 6.0f : k; m = kmc_clamp01(fminf(k, 4.0f - k)); r = km_fma(-vs, m, v);
-    k = h6 + 3.0f; k = k >= 6.0f ? k - 6.0f : k; m = kmc_clamp01(fminf(k, 4.0f - k)); g = km_fma(-vs, m, v);
-    k = h6 + 1.0f; k = k >= 6.0f ? k - 6.0f : k; m = kmc_clamp01(fminf(k, 4.0f - k)); b = km_fma(-vs, m, v);
+    k = h6 + 5.0f; k = k >= 6.0f ? k - 6.0f : k; m = kmc_sat01(fminf(k, 4.0f - k)); r = km_fma(-vs, m, v);
+    k = h6 + 3.0f; k = k >= 6.0f ? k - 6.0f : k; m = kmc_sat01(fminf(k, 4.0f - k)); g = km_fma(-vs, m, v);
+    k = h6 + 1.0f; k = k >= 6.0f ? k - 6.0f : k; m = kmc_sat01(fminf(k, 4.0f - k)); b = km_fma(-vs, m, v);
 }
 
-// applies stages [first, last) to one pixel; `mean` is used by the contrast stage.  FAST: kmc_hue_fast (16-bit storage)
-template <bool FAST = false>
-__device__ __forceinline__ void kmc_apply(float& r, float& g, float& b, const int (&stages)[KMC_MAX_STAGES], int first, int last,
+// Pixels that cannot meet a NaN on the way.  A NaN before a clamp or in front of the hue stage needs a NaN / inf going in: inf - inf, 0 x inf
+// or inf / inf (0 / 0 in rgb_to_hsv needs max + 1e-8 = 0, a negative maximum).  With every channel in [+0, 2) - images and the staged
+// intermediate lie in [0, 1] - and every factor and the mean finite and below 1e18 in magnitude, no product or sum of a stage reaches 3.4e38,
+// the three clamped stages return [0, 1] and the hue stage returns values between 0 and its input's maximum: by induction over the stages
+// nothing non-finite appears, and the stage chain with plain fminf / fmaxf (EXACT = false) gives the same bits as the NaN-keeping one.
+// [+0, 2) is "sign bit and top exponent bit clear", in fp32 and in both 16-bit formats (2.0 is 0x4000 in bf16 and in f16), so the test is an
+// OR over a lane's values and one mask: for 16-bit storage over the 6 packed dwords as they were loaded (KMC_TAME_MASK16), about 5 vector
+// instructions per 4 pixels.  A wave takes the plain chain when all of its lanes pass, else the NaN-keeping one.
+#define KMC_TAME_MASK32 0xc0000000u
+#define KMC_TAME_MASK16 0xc000c000u
+#define KMC_FACTOR_LIMIT_BITS 0x5d5e0b6bu  // 1e18f
+__device__ __forceinline__ bool kmc_tame_uniform(const float (&f)[4], float mean) {
+    uint32_t m = max(__float_as_uint(f[0]) & 0x7fffffffu, __float_as_uint(f[1]) & 0x7fffffffu);
+    m = max(m, max(__float_as_uint(f[2]) & 0x7fffffffu, __float_as_uint(f[3]) & 0x7fffffffu));
+    return max(m, __float_as_uint(mean) & 0x7fffffffu) < KMC_FACTOR_LIMIT_BITS;
+}
+
+// applies stages [first, last) to a lane's VEC pixels, stage by stage (the wave-uniform dispatch runs once per stage, not once per pixel, and
+// the VEC pixels of a stage are independent instruction streams); `mean` is used by the contrast stage.  FAST: kmc_hue_fast (16-bit
+// storage);  EXACT: clamps and channel extrema keep a NaN as torch's do (false: only for waves that passed the vote)
+template <bool FAST, bool EXACT, int VEC>
+__device__ __forceinline__ void kmc_apply(float (&r)[VEC], float (&g)[VEC], float (&b)[VEC], const int (&stages)[KMC_MAX_STAGES], int first, int last,
                                           const float (&f)[4], float mean, uint32_t enable_mask) {
     for (int s = first; s < last; ++s) {
         const int st = stages[s];  // wave-uniform
         if (!((enable_mask >> st) & 1u)) continue;
         if (st == KMC_BRIGHTNESS) {
-            r = kmc_clamp01(r * f[0]); g = kmc_clamp01(g * f[0]); b = kmc_clamp01(b * f[0]);
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) { r[q] = kmc_clamp<EXACT>(r[q] * f[0]); g[q] = kmc_clamp<EXACT>(g[q] * f[0]); b[q] = kmc_clamp<EXACT>(b[q] * f[0]); }
         } else if (st == KMC_CONTRAST) {
             const float off = mean * (1.0f - f[1]);
-            r = kmc_clamp01(r * f[1] + off); g = kmc_clamp01(g * f[1] + off); b = kmc_clamp01(b * f[1] + off);
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) { r[q] = kmc_clamp<EXACT>(r[q] * f[1] + off); g[q] = kmc_clamp<EXACT>(g[q] * f[1] + off); b[q] = kmc_clamp<EXACT>(b[q] * f[1] + off); }
         } else if (st == KMC_SATURATION) {
-            const float gr = kmc_gray(r, g, b), a = (1.0f - f[2]) * gr;
-            r = kmc_clamp01(a + f[2] * r); g = kmc_clamp01(a + f[2] * g); b = kmc_clamp01(a + f[2] * b);
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) {
+                const float gr = kmc_gray(r[q], g[q], b[q]), a = (1.0f - f[2]) * gr;
+                r[q] = kmc_clamp<EXACT>(a + f[2] * r[q]); g[q] = kmc_clamp<EXACT>(a + f[2] * g[q]); b[q] = kmc_clamp<EXACT>(a + f[2] * b[q]);
+            }
         } else {
-            if (FAST) kmc_hue_fast(r, g, b, f[3]);
-            else kmc_hue(r, g, b, f[3]);
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) {
+                if (FAST) kmc_hue_fast<EXACT>(r[q], g[q], b[q], f[3]);
+                else kmc_hue<EXACT>(r[q], g[q], b[q], f[3]);
+            }
         }
     }
 }
@@ -185,22 +245,44 @@ __global__ __launch_bounds__(256) void km_color_jitter_kernel(const KmColorArgs<
     const int start = (int)chunk * per_block;
     // (not unrolled: four inlined copies of the stage machine - exact fmod paths included - are ~45 KB of code, more than the
     // instruction cache of a CU pair holds)
+    constexpr bool FAST = KMC_FAST16 && sizeof(T) == 2;
+    const bool tame_uniform = kmc_tame_uniform(f, mean);  // block-uniform
 #pragma unroll 1
     for (int it = 0; it < 4; ++it) {
-        const int p0 = start + (it * 256 + (int)threadIdx.x) * VEC;
-        if (p0 >= HW) break;
+        const int base = start + it * 256 * VEC;  // block-uniform
+        if (base >= HW) break;
+        const int p0 = base + (int)threadIdx.x * VEC;
+        // no lane leaves before the wave vote below: a lane past the image's end works on the iteration's first pixels again (in range and,
+        // for VEC = 4, aligned: HW % 4 == 0) and stores nothing
+        const bool live = p0 < HW;
+        const int pl = live ? p0 : base;
         float r[VEC], g[VEC], bl[VEC];
         if constexpr (VEC == 4) {
-            km_ld4(in + p0, r);
-            km_ld4(in + HW + p0, g);
-            km_ld4(in + 2 * (size_t)HW + p0, bl);
+            km_ld4(in + pl, r);
+            km_ld4(in + HW + pl, g);
+            km_ld4(in + 2 * (size_t)HW + pl, bl);
         } else {
-            r[0] = (float)km_ld(in + p0); g[0] = (float)km_ld(in + HW + p0); bl[0] = (float)km_ld(in + 2 * (size_t)HW + p0);
+            r[0] = (float)km_ld(in + pl); g[0] = (float)km_ld(in + HW + pl); bl[0] = (float)km_ld(in + 2 * (size_t)HW + pl);
         }
+        uint32_t ob = 0u, mask = KMC_TAME_MASK32;
+        if constexpr (VEC == 4 && sizeof(T) == 2) {  // the packed words km_ld4 has just loaded (the same loads: merged by the compiler)
+            const uint2 w0 = *reinterpret_cast<const uint2*>(in + pl), w1 = *reinterpret_cast<const uint2*>(in + HW + pl),
+                        w2 = *reinterpret_cast<const uint2*>(in + 2 * (size_t)HW + pl);
+            ob = (w0.x | w0.y | w1.x) | (w1.y | w2.x | w2.y);
+            mask = KMC_TAME_MASK16;
+        } else {
 #pragma unroll
-        for (int q = 0; q < VEC; ++q) {
-            kmc_apply<(KMC_FAST16 && sizeof(T) == 2)>(r[q], g[q], bl[q], a.stages, first, last, f, mean, enable_mask);
-            if (MODE == 0) {
+            for (int q = 0; q < VEC; ++q) ob |= __float_as_uint(r[q]) | __float_as_uint(g[q]) | __float_as_uint(bl[q]);
+        }
+        if (__builtin_expect(tame_uniform && __all((ob & mask) == 0u), 1)) {  // wave-uniform
+            kmc_apply<FAST, false, VEC>(r, g, bl, a.stages, first, last, f, mean, enable_mask);
+        } else {
+            kmc_apply<FAST, true, VEC>(r, g, bl, a.stages, first, last, f, mean, enable_mask);
+        }
+        if (!live) continue;
+        if (MODE == 0) {
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) {
                 if (ci > 0) {  // the gray sum is taken of the values the apply pass will read back: the stored ones
                     r[q] = kmc_storage_round<T>(r[q]); g[q] = kmc_storage_round<T>(g[q]); bl[q] = kmc_storage_round<T>(bl[q]);
                 }
@@ -313,7 +395,8 @@ __device__ __forceinline__ KmcD kd_one_minus(const KmcD& a) { return {1.0f - a.v
 __device__ __forceinline__ void kmc_hue_jacobian(float r, float g, float b, float shift, float (&J)[3][4]) {
     const float two_pi = 6.283185307179586f;
     const KmcD R = {r, {1.f, 0.f, 0.f, 0.f}}, G = {g, {0.f, 1.f, 0.f, 0.f}}, B = {b, {0.f, 0.f, 1.f, 0.f}};
-    const float mxv = fmaxf(r, fmaxf(g, b)), mnv = fminf(r, fminf(g, b));
+    float mxv, mnv;
+    kmc_max_min(r, g, b, mxv, mnv);
     const float xr = (r == mxv) ? 1.f : 0.f, xg = (g == mxv) ? 1.f : 0.f, xb = (b == mxv) ? 1.f : 0.f, xc = 1.0f / fmaxf(xr + xg + xb, 1.0f);
     const float nr = (r == mnv) ? 1.f : 0.f, ng = (g == mnv) ? 1.f : 0.f, nb = (b == mnv) ? 1.f : 0.f, nc = 1.0f / fmaxf(nr + ng + nb, 1.0f);
     const KmcD MX = {mxv, {xr * xc, xg * xc, xb * xc, 0.f}}, MN = {mnv, {nr * nc, ng * nc, nb * nc, 0.f}};
@@ -365,7 +448,9 @@ struct KmColorBwdArgs {
     uint32_t blocks_per_image, nblocks;
 };
 
-__device__ __forceinline__ float kmc_pass01(float u) { return ((u >= 0.0f) && (u <= 1.0f)) ? 1.0f : 0.0f; }
+// clamp's backward is a SELECT (ATen: where(min <= u <= max, grad, 0)), not a product with a 0 / 1 mask: outside the bounds - and for a NaN
+// u, which no bound holds - the gradient is 0 even when grad is NaN or infinite
+__device__ __forceinline__ float kmc_pass01(float g, float u) { return ((u >= 0.0f) && (u <= 1.0f)) ? g : 0.0f; }
 
 // MODE 0: S of the contrast stage;  MODE 1: the gradients
 template <typename T, int MODE, int VEC>
@@ -444,12 +529,12 @@ __global__ __launch_bounds__(256) void km_color_jitter_bwd_kernel(const KmColorB
                 if (done) continue;
                 const float x0 = in[s][0], x1 = in[s][1], x2 = in[s][2];
                 if (st[s] == KMC_BRIGHTNESS) {
-                    const float m0 = gr3[0] * kmc_pass01(x0 * f[0]), m1 = gr3[1] * kmc_pass01(x1 * f[0]), m2 = gr3[2] * kmc_pass01(x2 * f[0]);
+                    const float m0 = kmc_pass01(gr3[0], x0 * f[0]), m1 = kmc_pass01(gr3[1], x1 * f[0]), m2 = kmc_pass01(gr3[2], x2 * f[0]);
                     gf[0] += (m0 * x0 + m1 * x1) + m2 * x2;
                     gr3[0] = m0 * f[0]; gr3[1] = m1 * f[0]; gr3[2] = m2 * f[0];
                 } else if (st[s] == KMC_CONTRAST) {
                     const float off = mean * (1.0f - f[1]);
-                    const float m0 = gr3[0] * kmc_pass01(x0 * f[1] + off), m1 = gr3[1] * kmc_pass01(x1 * f[1] + off), m2 = gr3[2] * kmc_pass01(x2 * f[1] + off);
+                    const float m0 = kmc_pass01(gr3[0], x0 * f[1] + off), m1 = kmc_pass01(gr3[1], x1 * f[1] + off), m2 = kmc_pass01(gr3[2], x2 * f[1] + off);
                     if (MODE == 0) {
                         acc_s += (m0 + m1) + m2;
                         done = true;
@@ -460,7 +545,7 @@ __global__ __launch_bounds__(256) void km_color_jitter_bwd_kernel(const KmColorB
                     }
                 } else if (st[s] == KMC_SATURATION) {
                     const float gray = kmc_gray(x0, x1, x2), aa = (1.0f - f[2]) * gray;
-                    const float m0 = gr3[0] * kmc_pass01(aa + f[2] * x0), m1 = gr3[1] * kmc_pass01(aa + f[2] * x1), m2 = gr3[2] * kmc_pass01(aa + f[2] * x2);
+                    const float m0 = kmc_pass01(gr3[0], aa + f[2] * x0), m1 = kmc_pass01(gr3[1], aa + f[2] * x1), m2 = kmc_pass01(gr3[2], aa + f[2] * x2);
                     gf[2] += (m0 * (x0 - gray) + m1 * (x1 - gray)) + m2 * (x2 - gray);
                     const float sm = (1.0f - f[2]) * ((m0 + m1) + m2);
                     gr3[0] = wgt[0] * sm + f[2] * m0; gr3[1] = wgt[1] * sm + f[2] * m1; gr3[2] = wgt[2] * sm + f[2] * m2;

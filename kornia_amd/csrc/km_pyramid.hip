@@ -112,6 +112,15 @@ __global__ __launch_bounds__(256) void km_pyrdown_kernel(const KmPyrArgs<T> a) {
     km_st(a.y + ((size_t)bc * a.oh + oy) * a.ow + ox, h0 * top + h1 * bot);
 }
 
+// An axis that keeps its size: ATen's upsample_bilinear2d (forward and backward) gives both taps the pixel itself, weights (1, 0), not
+// the pixel and its right / lower neighbour - so an inf / NaN does not reach the pixel before it (0 x inf = NaN), and an inf becomes NaN
+// where it stands.  Finite data cannot tell the two apart.
+template <typename R>
+__device__ __forceinline__ void kmp_axis_resize(int d, int n_in, int n_out, int align, int& i0, int& i1, R& l0, R& l1) {
+    kmp_axis<R>(d, n_in, n_out, align, i0, i1, l0, l1);
+    if (n_in == n_out) { i0 = i1 = d; l0 = (R)1; l1 = (R)0; }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void km_resize_bilinear_kernel(const KmPyrArgs<T> a) {
     typedef typename KmTraits<T>::R R;
@@ -122,8 +131,8 @@ __global__ __launch_bounds__(256) void km_resize_bilinear_kernel(const KmPyrArgs
     const T* img = a.x + (size_t)bc * H * W;
     int y0, y1, x0, x1;
     R h0, h1, w0, w1;
-    kmp_axis<R>(oy, H, a.oh, a.align, y0, y1, h0, h1);
-    kmp_axis<R>(ox, W, a.ow, a.align, x0, x1, w0, w1);
+    kmp_axis_resize<R>(oy, H, a.oh, a.align, y0, y1, h0, h1);
+    kmp_axis_resize<R>(ox, W, a.ow, a.align, x0, x1, w0, w1);
     const T* r0 = img + (size_t)y0 * W;
     const T* r1 = img + (size_t)y1 * W;
     const R v00 = (R)km_ld(r0 + x0), v01 = (R)km_ld(r0 + x1), v10 = (R)km_ld(r1 + x0), v11 = (R)km_ld(r1 + x1);
@@ -310,8 +319,9 @@ __global__ __launch_bounds__(256) void km_pyrdown2_sep_kernel(const KmPyrArgs<T>
 // 2s-1, 2s read source rows s-1, s.  A lane owns 2 source columns (4 output columns, one 16-byte store), a wave walks a strip
 // of source rows keeping the horizontally interpolated previous row in registers: every source row is loaded once per
 // lane (+2 halo rows per strip) instead of 4 gathered loads per output pixel.  Indices and weights still come from
-// kmp_axis, so the borders (weights (1, 0) on the first row / column, repeated index on the last) need no special case;
-// where kmp_axis gives weight 0 the neighbour loaded here may differ from ATen's, which is exact for finite data.
+// kmp_axis, and so do the PIXELS behind the two zero weights: output column 0 is 1 x column 0 + 0 x column 1 and output row 0 is
+// 1 x row 0 + 0 x row 1 in ATen and in the general kernel, so an inf / NaN in column 1 or row 1 reaches them (0 x inf = NaN) - the
+// lane of column 0 takes its own second column there, and output row 0 is written one step later, from source rows 0 and 1.
 template <typename T>
 __global__ __launch_bounds__(256) void km_resize2x_kernel(const KmPyrArgs<T> a) {
     typedef typename KmTraits<T>::R R;
@@ -346,14 +356,18 @@ __global__ __launch_bounds__(256) void km_resize2x_kernel(const KmPyrArgs<T> a) 
         km_ld2(rowp + c0, m0, m1);
         const R vl = (R)km_ld(rowp + cl), vr = (R)km_ld(rowp + cr);
         R cur[4];
-        cur[0] = w0[0] * vl + w1[0] * m0;
+        cur[0] = w0[0] * vl + w1[0] * (c0 > 0 ? m0 : m1);  // (c0 == 0: vl is column 0, weights (1, 0))
         cur[1] = w0[1] * m0 + w1[1] * m1;
         cur[2] = w0[2] * m0 + w1[2] * m1;
         cur[3] = w0[3] * m1 + w1[3] * vr;
         if (s >= s0) {
 #pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int oy = 2 * s - 1 + half;  // rows 2s-1 and 2s are interpolated between source rows s-1 and s
+            for (int half = 0; half < 3; ++half) {
+                // rows 2s-1 and 2s are interpolated between source rows s-1 and s; row 0 between rows 0 and 1 with weights (1, 0), so it
+                // is written at s = 1 (half 2), where prev is row 0 and cur is row 1 (H >= 2: s = 1 is a step of the first strip)
+                if (half == 2 && s != 1) continue;
+                const int oy = half == 2 ? 0 : 2 * s - 1 + half;
+                if (s == 0 && half == 1) continue;
                 if (oy >= 2 * s0 && oy < 2 * s1) {
                     int y0, y1;
                     R h0, h1;
@@ -445,6 +459,7 @@ static int kmp_run(bool blur, const void* x, void* y, int B, int C, int H, int W
 // forward's own arithmetic (so that rounding can neither drop nor double-count an output).
 template <typename R>
 __device__ __forceinline__ void kmp_adjoint_range(int i, int n_in, int n_out, int align, int& lo, int& hi) {
+    if (n_in == n_out) { lo = hi = i; return; }  // kmp_axis_resize: output i alone reads input i
     // estimate of the first output whose i0 >= i - 1 / last whose i0 <= i
     const R scale = align ? (n_out > 1 ? (R)(n_in - 1) / (R)(n_out - 1) : (R)0) : (R)n_in / (R)n_out;
     int a, b;
@@ -464,11 +479,15 @@ __device__ __forceinline__ void kmp_adjoint_range(int i, int n_in, int n_out, in
     while (hi < n_out - 1) { kmp_axis<R>(hi + 1, n_in, n_out, align, i0, i1, l0, l1); if (i0 <= i) ++hi; else break; }
     while (hi > lo) { kmp_axis<R>(hi, n_in, n_out, align, i0, i1, l0, l1); if (i0 > i) --hi; else break; }
 }
+// output d's contribution v to input i along one axis, added to acc term by term as ATen's scatter does: l0 v to i0 and l1 v to i1, each
+// also where the weight is 0 (0 x inf = NaN reaches the pixel) and both where i1 == i0 (the last row / column)
 template <typename R>
-__device__ __forceinline__ R kmp_adjoint_weight(int d, int i, int n_in, int n_out, int align) {
+__device__ __forceinline__ R kmp_adjoint_add(R acc, R v, int d, int i, int n_in, int n_out, int align) {
     int i0, i1; R l0, l1;
-    kmp_axis<R>(d, n_in, n_out, align, i0, i1, l0, l1);
-    return (i0 == i ? l0 : (R)0) + (i1 == i ? l1 : (R)0);  // (i1 == i0 on the last row: both weights land on it)
+    kmp_axis_resize<R>(d, n_in, n_out, align, i0, i1, l0, l1);
+    if (i0 == i) acc = acc + l0 * v;
+    if (i1 == i) acc = acc + l1 * v;
+    return acc;
 }
 
 template <typename T>
@@ -485,14 +504,9 @@ __global__ __launch_bounds__(256) void km_resize_bilinear_bwd_kernel(const T* __
     const T* g = gy + (size_t)bc * oh * ow;
     R acc = (R)0;
     for (int d = ylo; d <= yhi; ++d) {
-        const R wy = kmp_adjoint_weight<R>(d, (int)i, H, oh, align);
-        if (wy == (R)0) continue;
         R row = (R)0;
-        for (int e = xlo; e <= xhi; ++e) {
-            const R wx = kmp_adjoint_weight<R>(e, j, W, ow, align);
-            row = row + wx * (R)km_ld(g + (size_t)d * ow + e);
-        }
-        acc = acc + wy * row;
+        for (int e = xlo; e <= xhi; ++e) row = kmp_adjoint_add<R>(row, (R)km_ld(g + (size_t)d * ow + e), e, j, W, ow, align);
+        acc = kmp_adjoint_add<R>(acc, row, d, (int)i, H, oh, align);
     }
     km_st(gx + ((size_t)bc * H + i) * W + j, acc);
 }

@@ -642,6 +642,9 @@ static inline void KO(ko_resize_axis)(int d, int n_in, int n_out, int align, int
     *i1 = *i0 + (*i0 < n_in - 1 ? 1 : 0);
     *l1 = src - (REAL)*i0;
     *l0 = (REAL)1 - *l1;
+    /* an axis that keeps its size: ATen gives both taps the pixel itself, weights (1, 0) - an inf / NaN neighbour does not reach the
+     * pixel in front of it, and an inf becomes NaN (0 x inf) where it stands; finite data cannot tell */
+    if (n_in == n_out) { *i0 = *i1 = d; *l0 = (REAL)1; *l1 = (REAL)0; }
 }
 
 void KO(ko_resize_bilinear_fwd)(const REAL* x, REAL* y, int BC, int H, int W, int oh, int ow, int align) {
