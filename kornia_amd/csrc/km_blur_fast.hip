@@ -28,11 +28,7 @@
 #include "km_regtile.h"
 
 
-#ifdef KMB_ROWS_OVERRIDE
-#define KMB_ROWS KMB_ROWS_OVERRIDE
-#else
 #define KMB_ROWS 32  // output rows per thread (strip height) of the large form
-#endif
 // A wave walks its strip row by row: (ROWS + K - 1) / ROWS input rows are read per output row (the extra ones mostly L2 hits), and a launch with few
 // waves per SIMD has little to overlap its row loads with.  Three strip heights are compiled - 32, 16 and 8 rows - and km_blur_rows() picks one per
 // launch from what profiles/r04/run49_blur_strip_heights.txt measured (round 2 had measured 8 -> 0.32 ms, 16 -> 0.31, 32 -> 0.295 at 256x3x512^2 on the
@@ -106,11 +102,8 @@ __device__ __forceinline__ void kmb_adjoint_taps(const float (&k)[K], int p, int
     }
 }
 
-#ifndef KMB_BWD_WAVES
-#define KMB_BWD_WAVES 1   // minimum waves per SIMD asked of the adjoint's register allocation (8: at most 64 registers)
-#endif
 template <typename T, int K, bool BWD, int ROWS = KMB_ROWS>
-__global__ __launch_bounds__(256, (BWD ? KMB_BWD_WAVES : 1)) void km_blur_reg_kernel(const KmBlurArgs<T> a) {
+__global__ __launch_bounds__(256, 1) void km_blur_reg_kernel(const KmBlurArgs<T> a) {
     constexpr int L = (K - 1) / 2, R = K - 1 - L;
     constexpr bool COLF = BWD && sizeof(T) == 2;  // column adjoint first, rounded to T (see the head of the file)
     uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks, a.reverse);

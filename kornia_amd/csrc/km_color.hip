@@ -105,9 +105,6 @@ __device__ __forceinline__ void kmc_hue(float& r, float& g, float& b, float shif
 // that both reductions are x - floor(x), and the standard branch-free HSV -> RGB  c_n = v - v s clamp(min(k, 4 - k), 0, 1),
 // k = (n + 6 h) mod 6, n = 5 / 3 / 1 for r / g / b.  ~45 instructions; within ~1e-6 of kmc_hue before the storage rounding (a different
 // 16-bit neighbour at ties: tests/test_gpu_color.py compares at the storage type's 1e-2).  fp32 storage keeps kmc_hue.
-#ifndef KMC_FAST16
-#define KMC_FAST16 1
-#endif
 __device__ __forceinline__ float kmc_rcp(float v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_rcpf(v);
@@ -245,7 +242,7 @@ __global__ __launch_bounds__(256) void km_color_jitter_kernel(const KmColorArgs<
     const int start = (int)chunk * per_block;
     // (not unrolled: four inlined copies of the stage machine - exact fmod paths included - are ~45 KB of code, more than the
     // instruction cache of a CU pair holds)
-    constexpr bool FAST = KMC_FAST16 && sizeof(T) == 2;
+    constexpr bool FAST = sizeof(T) == 2;
     const bool tame_uniform = kmc_tame_uniform(f, mean);  // block-uniform
 #pragma unroll 1
     for (int it = 0; it < 4; ++it) {

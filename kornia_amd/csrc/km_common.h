@@ -68,13 +68,6 @@ __device__ __forceinline__ float km_next64(float v) { return __uint_as_float(km_
 __device__ __forceinline__ float km_prev64(float v) {
     return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp((int)__float_as_uint(v), (int)__float_as_uint(v), 0x138, 0xf, 0xf, false));
 }
-// Value held by lane ^ 1 / lane ^ 2 of the same QUAD of lanes (DPP quad_perm [1,0,3,2] / [2,3,0,1]: one VALU move each)
-__device__ __forceinline__ float km_quad_xor1(float v) {
-    return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp((int)__float_as_uint(v), (int)__float_as_uint(v), 0xB1, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float km_quad_xor2(float v) {
-    return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp((int)__float_as_uint(v), (int)__float_as_uint(v), 0x4E, 0xf, 0xf, false));
-}
 // Maximum of an unsigned value over the wave, valid in LANE 63 only (other lanes hold partial maxima): an inclusive scan inside each row
 // of 16 lanes (row_shr:1/2/4/8; a lane without a source keeps its own value), then lane 15 of a row into the next row (row_bcast:15,
 // rows 1 and 3) and lane 31 into rows 2 and 3 (row_bcast:31) - ten VALU instructions, no LDS traffic (a __shfl_down ladder is six
@@ -103,34 +96,6 @@ __device__ __forceinline__ double km_wave_sum_last(double v) {
     return v;
 }
 #endif
-
-// 4 x 4 transpose inside a quad of lanes: lane q (= lane & 3) enters with a[r] = element (row r, column q) of a 4 x 4 block and leaves with
-// a[k] = element (row q, column k) - its own ROW of the block, i.e. four horizontally adjacent pixels for ONE 16-byte store where the
-// lane = column layout of the sampling kernels would issue four 4-byte ones.  Two butterfly stages (lane bit 0 <-> register bit 0, lane bit 1
-// <-> register bit 1): 4 quad-permute moves + 12 selects, no LDS.  All four lanes of the quad must be active.
-__device__ __forceinline__ void km_quad_transpose4(float (&a)[4], int q) {
-    const bool b0 = (q & 1) != 0, b1 = (q & 2) != 0;
-#pragma unroll
-    for (int p = 0; p < 4; p += 2) {  // register pairs (0,1), (2,3) with lane ^ 1
-        const float r = km_quad_xor1(b0 ? a[p] : a[p + 1]);
-        a[p] = b0 ? r : a[p];
-        a[p + 1] = b0 ? a[p + 1] : r;
-    }
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {     // register pairs (0,2), (1,3) with lane ^ 2
-        const float r = km_quad_xor2(b1 ? a[p] : a[p + 2]);
-        a[p] = b1 ? r : a[p];
-        a[p + 2] = b1 ? a[p + 2] : r;
-    }
-}
-// four horizontally adjacent fp32 pixels with one 16-byte store (p 16-byte aligned), streaming or plain (km_st_c's policy)
-template <bool STREAM>
-__device__ __forceinline__ void km_st4_c(float* p, const float (&v)[4]) {
-    typedef float km_f4v_ __attribute__((ext_vector_type(4)));
-    km_f4v_ vv; vv.x = v[0]; vv.y = v[1]; vv.z = v[2]; vv.w = v[3];
-    if constexpr (STREAM) __builtin_nontemporal_store(vv, reinterpret_cast<km_f4v_*>(p));
-    else *reinterpret_cast<km_f4v_*>(p) = vv;
-}
 
 // ---- storage types ----------------------------------------------------------------------------
 struct km_bf16 {
@@ -199,36 +164,21 @@ __device__ __forceinline__ uint32_t km_f32x2_to_bf16x2_bits(float lo, float hi) 
 // Outputs are written once and read by the NEXT kernel, after ~0.8 GB of other traffic at the hot sizes: streaming (non-temporal)
 // stores keep them from displacing the lines the running kernel still needs in L2.  Measured on MI355X, config 2, same box: step
 // 1.798 -> 1.744 ms (forward 0.384 -> 0.370, blur 0.332 -> 0.319, blur adjoint 0.332 -> 0.323, scatter 0.398 -> 0.391 ms).
-// Non-temporal LOADS measured slower (blur 0.332 -> 0.35 ms; grad_out in the scatter, which reads it once: step 1.64 -> 1.67 ms).  -DKM_NO_NT_ST builds with plain stores (A/B).
-#ifndef KM_NO_NT_ST
-#define KM_NT_ST 1
-#endif
-#ifdef KM_NT_ST
+// Non-temporal LOADS measured slower (blur 0.332 -> 0.35 ms; grad_out in the scatter, which reads it once: step 1.64 -> 1.67 ms).
 __device__ __forceinline__ void km_st(float* p, float v) { __builtin_nontemporal_store(v, p); }
-#else
-__device__ __forceinline__ void km_st(float* p, float v) { *p = v; }
-#endif
 // The three kernels of the hot step choose per launch: an output that fits in the 256 MB Infinity Cache with room to spare is what the next
 // kernel will find there, and streaming it out costs that (config 2 at B = 16, 50 MB tensors: step 0.152 ms with plain stores, 0.166 ms with
 // streaming ones; B = 64, 201 MB: 0.486 / 0.478; B = 256, 805 MB: 1.74 / 1.69).  stream = km_stream_stores(bytes of the output), wave-uniform.
 #define KM_STREAM_MIN_BYTES (128ull << 20)
 static inline uint32_t km_stream_stores(uint64_t out_bytes) {
-#ifdef KM_NT_ST
     return out_bytes >= KM_STREAM_MIN_BYTES ? 1u : 0u;
-#else
-    (void)out_bytes;
-    return 0u;
-#endif
 }
 // The policy as a COMPILE-TIME parameter.  (Round 2's form - a bool argument, `if (stream) nontemporal_store else plain store` - compiled to
 // plain stores in every instantiation: the two stores of the if / else are merged into one before the constant reaches them, and the merge
 // drops the non-temporal mark; found in round 3 by reading the ISA of the forward - its hot path had not streamed a byte since.)
-#ifndef KM_FWD_PLAIN_ST
-#define KM_FWD_PLAIN_ST 0   // 1: the forward's compile-time policy is forced to plain stores (A/B against round 2's accidental behaviour)
-#endif
 template <bool STREAM>
 __device__ __forceinline__ void km_st_c(float* p, float v) {
-    if constexpr (STREAM && !KM_FWD_PLAIN_ST) __builtin_nontemporal_store(v, p);
+    if constexpr (STREAM) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
 __device__ __forceinline__ void km_st(double* p, double v) { *p = v; }
@@ -384,9 +334,7 @@ __device__ __forceinline__ void km_glds4(const void* gsrc, uint32_t lds_dst) {
 #ifndef KM_TID_PINNED
 __device__ __forceinline__ int km_tid_pinned() {
     int t = (int)threadIdx.x;
-#ifndef KM_TID_UNPINNED
     asm volatile("" : "+v"(t));
-#endif
     return t;
 }
 #endif

@@ -41,26 +41,18 @@ __device__ __forceinline__ void km_ld4(const km_f16* p, float (&o)[4]) {
 }
 __device__ __forceinline__ void km_st4(float* p, const float (&o)[4]) {
     KM_CHECK_ALIGNED(p, 16);
-#ifdef KM_NT_ST
     typedef float km_f4v __attribute__((ext_vector_type(4)));
     km_f4v v; v.x = o[0]; v.y = o[1]; v.z = o[2]; v.w = o[3];
     __builtin_nontemporal_store(v, reinterpret_cast<km_f4v*>(p));
-#else
-    *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
-#endif
 }
 __device__ __forceinline__ void km_st4(km_bf16* p, const float (&o)[4]) {
     uint2 v;
     v.x = km_f32x2_to_bf16x2_bits(o[0], o[1]);
     v.y = km_f32x2_to_bf16x2_bits(o[2], o[3]);
     KM_CHECK_ALIGNED(p, 8);
-#ifdef KM_NT_ST
     typedef uint32_t km_u2v __attribute__((ext_vector_type(2)));
     km_u2v vv; vv.x = v.x; vv.y = v.y;
     __builtin_nontemporal_store(vv, reinterpret_cast<km_u2v*>(p));
-#else
-    *reinterpret_cast<uint2*>(p) = v;
-#endif
 }
 // fp32 result -> f16, never fused with the arithmetic that produced it (km_common.h, km_st(km_f16*, float))
 __device__ __forceinline__ _Float16 km_f16_of(float v) { KM_OPAQUE(v); return (_Float16)v; }
@@ -69,11 +61,7 @@ __device__ __forceinline__ void km_st4(km_f16* p, const float (&o)[4]) {
     h4 v;
     v.x = km_f16_of(o[0]); v.y = km_f16_of(o[1]); v.z = km_f16_of(o[2]); v.w = km_f16_of(o[3]);
     KM_CHECK_ALIGNED(p, 8);
-#ifdef KM_NT_ST
     __builtin_nontemporal_store(v, reinterpret_cast<h4*>(p));
-#else
-    *reinterpret_cast<h4*>(p) = v;
-#endif
 }
 // km_st4 with the store policy chosen per launch (km_stream_stores): streaming or plain
 __device__ __forceinline__ void km_st4_pol(float* p, const float (&o)[4], bool stream) {
@@ -100,30 +88,18 @@ __device__ __forceinline__ void km_st4_pol(km_f16* p, const float (&o)[4], bool 
 // two adjacent pixels with one 8-byte / 4-byte store
 __device__ __forceinline__ void km_st2(float* p, float a, float b) {
     KM_CHECK_ALIGNED(p, 8);
-#ifdef KM_NT_ST
     typedef float km_f2v __attribute__((ext_vector_type(2)));
     km_f2v v; v.x = a; v.y = b;
     __builtin_nontemporal_store(v, reinterpret_cast<km_f2v*>(p));
-#else
-    *reinterpret_cast<float2*>(p) = make_float2(a, b);
-#endif
 }
 __device__ __forceinline__ void km_st2(km_bf16* p, float a, float b) {
     KM_CHECK_ALIGNED(p, 4);
-#ifdef KM_NT_ST
     __builtin_nontemporal_store(km_f32x2_to_bf16x2_bits(a, b), reinterpret_cast<uint32_t*>(p));
-#else
-    *reinterpret_cast<uint32_t*>(p) = km_f32x2_to_bf16x2_bits(a, b);
-#endif
 }
 __device__ __forceinline__ void km_st2(km_f16* p, float a, float b) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     h2 v;
     v.x = km_f16_of(a); v.y = km_f16_of(b);
     KM_CHECK_ALIGNED(p, 4);
-#ifdef KM_NT_ST
     __builtin_nontemporal_store(v, reinterpret_cast<h2*>(p));
-#else
-    *reinterpret_cast<h2*>(p) = v;
-#endif
 }

@@ -19,15 +19,11 @@
 #include "km_warp_args.h"
 #include "km_warp_stage.h"
 
-#ifndef KM_ROWS
 #define KM_ROWS 4   // output rows per thread
-#endif
 #define KM_TILE_W 64
 #define KM_TILE_H (4 * KM_ROWS)
-#ifndef KM_PATCH_W
 #define KM_PATCH_W 32  // output columns covered by one wave instruction of the specialised forward (64, 32 or 16);
                        // measured at 256x3x512^2: 64 -> 0.434 ms (0.78 at 20 deg rotation), 32 -> 0.422 (0.67), 16 -> 0.492 (0.64)
-#endif
 
 template <typename T, int CM, int INTERP>
 __global__ __launch_bounds__(256) void km_warp_fwd_kernel(const KmWarpArgs<T> a) {
@@ -440,15 +436,10 @@ __device__ __forceinline__ void km_warp_fwd_lean_rows(const KmWarpArgs<T>& a, co
 // and argument loads, the row table with its IEEE divisions, a barrier, ~2 us before the first pixel - is spread over
 // 64 x 16 x KML_GROUPS pixels (measured: the kernel is bound by these serial latencies and the memory latency behind them,
 // not by bytes or instructions).
-#ifndef KML_GROUPS
 #define KML_GROUPS 2   // measured on one box, 256x3x512^2: 1 -> 0.49 ms, 2 -> 0.41, 4 -> 0.42 (round-1 kernel there: 0.44)
-#endif
 #define KML_TILE_H (KM_TILE_H * KML_GROUPS)
-#ifndef KML_BOUNDS
-#define KML_BOUNDS __launch_bounds__(256)
-#endif
 template <typename T, int CM, int NC, int ALIGN>  // NC = 3 / 1: RGB / grey unrolled ; NC = 0: runtime channel loop
-__global__ KML_BOUNDS void km_warp_fwd_lean_kernel(const KmWarpArgs<T> a) {
+__global__ __launch_bounds__(256) void km_warp_fwd_lean_kernel(const KmWarpArgs<T> a) {
     static_assert(KML_TILE_H <= 64, "the row table is filled by one wave");
     const KmWarpGeom<float>& g = a.g;
     uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks, a.reverse);
@@ -702,30 +693,13 @@ static bool km_fwd_generic_forced() {
 //                 degrees: 0.37 - 0.39 ms where the gather kernel takes 0.47 / 0.71 / 0.92);
 //   3. the gather rows of km_warp_fwd_lean_kernel: for a half whose box still does not fit, and - before the squares are tried - for a region
 //      whose output rows stay nearly horizontal in the source (its wide box was too large because the map minifies: gathers are fine there).
-#ifndef KMB_WIDE_PITCH
-#define KMB_WIDE_PITCH 80
-#define KMB_WIDE_ROWS 40
-#endif
+#define KMB_WIDE_PITCH 80  // staged source box of the wide tile: floats per row,
+#define KMB_WIDE_ROWS 40   // rows
 struct KmbWide   { static constexpr int TW = 64, TH = 32, PITCH = KMB_WIDE_PITCH, ROWS = KMB_WIDE_ROWS; };
 struct KmbSquare { static constexpr int TW = 32, TH = 32, PITCH = 52, ROWS = 50; };
 #define KMB_LDS_FLOATS(NC) ((KmbWide::ROWS * KmbWide::PITCH > KmbSquare::ROWS * KmbSquare::PITCH ? KmbWide::ROWS * KmbWide::PITCH : KmbSquare::ROWS * KmbSquare::PITCH) * (NC))
-#ifndef KMB_WAVES_PER_EU
 #define KMB_WAVES_PER_EU 4   // what the LDS of a block allows (38 KB: 4 blocks of 4 waves per CU)
-#endif
-#ifndef KMB_TRY_WIDE
-#define KMB_TRY_WIDE 1       // 0: squares only (A/B)
-#endif
-#ifndef KMB_FILL_DMA
-#define KMB_FILL_DMA 1       // fp32 storage: the box by LDS-DMA (global_load_lds_dwordx4) instead of through registers
-#endif
-#ifndef KMB_ST16
-#define KMB_ST16 0           // 1: fp32 storage, a quad of lanes transposes its 4 x 4 results and stores 16 bytes per lane (0: one dword per lane and row).
-                             // MEASURED SLOWER (round 6, profiles/r06/run1_*: same box, bit-identical): flagship 312.0 / 313.1 us against 288.6 / 287.2,
-                             // 5 degrees 338 against 310, 20 degrees 422 against 386 - a quarter of the store instructions, 8 % more time: see DESIGN.md 4.6
-#endif
-#ifndef KMB_TILT_ROWS
 #define KMB_TILT_ROWS 4      // a region whose output rows span at most this many source rows takes the gather rows when its wide box does not fit
-#endif
 
 // the rows of a thread by gathers, one row at a time (plain IEEE divisions: any operands; every tap predicated): what a wave with a
 // footprint outside its box falls back to.  Deliberately small - the registers of the kernel are the maximum over its paths.
@@ -805,14 +779,10 @@ __device__ __forceinline__ void kmb_tile_body(const KmWarpArgs<T>& a, const floa
     const bool filler = (rq < RCPP) && (ck < bx.nch);
     const bool col_in = (xg >= 0) && (xg + 3 < W);  // W % 4 == 0 and xs % 4 == 0: a chunk is inside or outside as a whole
     const int nrc = bx.nrows * NC;
-#if KMB_FILL_DMA
     // fp32 storage: every chunk straight into LDS (KM_GLDS16: the wave's 64 pieces land at consecutive 16-byte cells - a pass of the block is
     // RCPP * NCHK consecutive chunks, thread t's at chunk t); no register holds the box on its way (40 of this kernel's 127), no ds_write pass.
     // Chunks outside the image are zeros, written the ordinary way.  The requests have landed after KM_VMCNT0() + the barrier below.
     constexpr bool DMA = sizeof(T) == 4;
-#else
-    constexpr bool DMA = false;
-#endif
     // (UNCONDITIONAL loads - a chunk outside the image or beyond the box reads the first chunk of the image and is replaced by zeros on its
     // way to LDS: with `v = 0; if (inside) load` the compiler keeps the whole array as one register tuple and copies - or spills - all of
     // it at every conditional definition)
@@ -876,67 +846,8 @@ __device__ __forceinline__ void kmb_tile_body(const KmWarpArgs<T>& a, const floa
     }
     __syncthreads();
     const bool all_in = __all(inbox);  // (by every lane of the wave: columns right of the image count as inside)
-#if KMB_ST16
-    if constexpr (sizeof(T) == 4) {
-        // 16-BYTE STORES (round 6).  The taps keep lane = output column (neighbouring lanes read neighbouring LDS banks); what changes is the
-        // way out: the thread's rows are taken four at a time, each quad of lanes transposes its 4 rows x 4 columns per channel in registers
-        // (km_quad_transpose4: quad-permute moves and selects - VALU this kernel has spare, profiles/r05_final_pmc_units.json: VALU 19 % busy,
-        // the texture-address unit 71 %, two thirds of its instructions these stores) and lane q of the quad writes row q's four pixels with
-        // ONE global_store_dwordx4: a quarter of the store instructions for the same bytes, the same values.
-        // Output rows must be 16-byte aligned runs of whole quads (block-uniform test); every lane of the wave walks the groups - lanes right
-        // of the image or below it compute nothing and store nothing, but take part in the transposes of their quad.
-        const bool vec16 = ((g.w & 3) == 0) && ((j0 & 3) == 0) && (((uintptr_t)a.dst & 15) == 0);
-        if (vec16 && all_in) {  // wave-uniform
-            static_assert(RPT % 4 == 0, "rows of a thread in groups of four");
-            const int q4 = tid & 3;
-            const bool col_ok = j < g.w;
-            const uint32_t outq = (uint32_t)i_base * (uint32_t)g.w + (uint32_t)(j & ~3);
-            float* __restrict__ dp[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) dp[c] = reinterpret_cast<float*>(dst_b) + c * dst_plane;
-#pragma unroll
-            for (int r0 = 0; r0 < RPT; r0 += 4) {
-                const bool grp_ok = col_ok && (i_base + r0 < g.h);  // (the tile hangs over the bottom / right edge of the image)
-                if (!__any(grp_ok)) break;                          // wave-uniform (the groups that follow lie lower still)
-                float acc[NC][4];
-#pragma unroll
-                for (int c = 0; c < NC; ++c)
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) acc[c][rr] = 0.f;
-                if (grp_ok) {
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) {
-                        // (a row below the image samples the group's first row again: its own position need not lie in the box; never stored)
-                        const bool rv = i_base + r0 + rr < g.h;
-                        KmlTaps t;
-                        kml_taps(rv ? xs[r0 + rr] : xs[r0], rv ? ys[r0 + rr] : ys[r0], t);
-                        const int xi = KM_F2I(t.xf) - bx.xs, yi = KM_F2I(t.yf) - bx.ys;
-                        const float* q0 = s_src + __mul24(yi, NC * PITCH) + xi;
-                        const float* q1 = q0 + NC * PITCH;
-                        const float w00 = t.wx1 * t.wy1, w01 = t.wx0 * t.wy1, w10 = t.wx1 * t.wy0, w11 = t.wx0 * t.wy0;
-#pragma unroll
-                        for (int c = 0; c < NC; ++c) {
-                            const float v00 = q0[c * PITCH], v01 = q0[c * PITCH + 1], v10 = q1[c * PITCH], v11 = q1[c * PITCH + 1];
-                            acc[c][rr] = km_fma(v11, w11, km_fma(v10, w10, km_fma(v01, w01, km_fma(v00, w00, 0.0f))));
-                        }
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < NC; ++c) km_quad_transpose4(acc[c], q4);
-                if (grp_ok && (i_base + r0 + q4 < g.h)) {
-                    const uint32_t oo = outq + (uint32_t)(r0 + q4) * (uint32_t)g.w;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        float* p = km_at_mut(dp[c], oo);
-                        KM_CHECK_ALIGNED(p, 16);
-                        km_st4_c<STREAM && !KM_FWD_PLAIN_ST>(p, acc[c]);
-                    }
-                }
-            }
-            return;
-        }
-    }
-#endif
+    // (One dword per lane and row.  16-byte stores after a 4 x 4 transpose inside each quad of lanes - a quarter of the store instructions,
+    // bit-identical - measured 8 % SLOWER: flagship 312 us against 288, profiles/r06/run1_*)
     if (j < g.w) {
         if (!all_in) {  // (never seen for boxes that fit; keeps the result independent of the box estimate)
             kmb_gather_rows<T, CM, NC, ALIGN, RPT>(a, m, s_rv, b, j, li_base, i_base);
@@ -967,9 +878,6 @@ __device__ __forceinline__ void kmb_tile_body(const KmWarpArgs<T>& a, const floa
     }
 }
 
-#ifndef KMB_PERSISTENT
-#define KMB_PERSISTENT 0     // 1: the launch is KMB_WAVES_PER_EU workgroups per CU, each walking its share of the regions (measured: slower, see below)
-#endif
 // one 64 x 32 region of the output (logical block `bid` of a.nblocks), by the whole workgroup
 template <typename T, int CM, int NC, int ALIGN, bool STREAM>
 __device__ __forceinline__ void kmb_region(const KmWarpArgs<T>& a, uint32_t bid, float4* s_rv, int* s_info, float* s_src) {
@@ -997,7 +905,7 @@ __device__ __forceinline__ void kmb_region(const KmWarpArgs<T>& a, uint32_t bid,
     __syncthreads();
     const KmfBox bxw = kmf_read_box(s_info);
     const int tilt = __builtin_amdgcn_readfirstlane(s_info[6]);  // source rows spanned by one output row of the region
-    if (KMB_TRY_WIDE && bxw.staged) {
+    if (bxw.staged) {
         kmb_tile_body<T, CM, NC, ALIGN, STREAM, KmbWide>(a, m, b, J0, I0, bxw, s_rv, s_src);
         return;
     }
@@ -1035,12 +943,9 @@ __device__ __forceinline__ void kmb_region(const KmWarpArgs<T>& a, uint32_t bid,
     }
 }
 
-
-// One workgroup per region.  (The counters say a workgroup lives 8.7 us and the CUs hold 11.1 of their 16 waves on average
-// (profiles/r05_pmc_units.json); KMB_PERSISTENT = 1 - KMB_WAVES_PER_EU workgroups per CU that WALK the regions, no dispatch between two of
-// them - was nevertheless 8 % SLOWER on the flagship maps and 25 - 45 % slower under rotation / minification, where regions differ in cost
-// and a fixed share per workgroup does not balance: profiles/r05/fwd_box_variants.txt.  The loop stays for that switch: the default launch
-// has one region per workgroup and runs it once.)
+// One workgroup per region.  (A persistent form - KMB_WAVES_PER_EU workgroups per CU that WALK the regions, no dispatch between two of them -
+// measured 8 % SLOWER on the flagship maps and 25 - 45 % slower under rotation / minification, where regions differ in cost and a fixed
+// share per workgroup does not balance: profiles/r05/fwd_box_variants.txt.)
 template <typename T, int CM, int NC, int ALIGN, bool STREAM>
 __global__ __launch_bounds__(256, KMB_WAVES_PER_EU) void km_warp_fwd_box_kernel(const KmWarpArgs<T> a) {
     static_assert(KmbWide::TH == KmbSquare::TH && KmbWide::TW == 2 * KmbSquare::TW, "a wide tile is two square ones side by side");
@@ -1048,16 +953,9 @@ __global__ __launch_bounds__(256, KMB_WAVES_PER_EU) void km_warp_fwd_box_kernel(
     __shared__ float4 s_rv[KmbWide::TH];
     __shared__ int s_info[8];
     __shared__ __attribute__((aligned(16))) float s_src[KMB_LDS_FLOATS(NC)];  // [row][channel][x]
-    // (inside the loop every helper takes its thread index through km_tid_pinned(): what depends on the thread index alone would otherwise be
-    // hoisted out of the loop and stay live across the whole body - 280 bytes of spills in a kernel that sits at its register limit)
-#if KMB_PERSISTENT
-    for (uint32_t lb = blockIdx.x; lb < a.nblocks; lb += gridDim.x) {
-        if (lb != blockIdx.x) __syncthreads();  // the previous region's readers are done with s_rv, s_info and s_src
-        kmb_region<T, CM, NC, ALIGN, STREAM>(a, km_xcd_remap(lb, a.nblocks, a.reverse), s_rv, s_info, s_src);
-    }
-#else
+    // (every helper takes its thread index through km_tid_pinned(): what depends on the thread index alone would otherwise be computed once
+    // and stay live across the whole body - 280 bytes of spills in a kernel that sits at its register limit)
     kmb_region<T, CM, NC, ALIGN, STREAM>(a, km_xcd_remap(blockIdx.x, a.nblocks, a.reverse), s_rv, s_info, s_src);
-#endif
 }
 
 // LDS-staged bicubic forward (km_warp_cubic.hip): launches and returns 1 when it takes the case, 0 otherwise
@@ -1090,12 +988,7 @@ static void km_warp_fwd_box_launch_nc(const KmWarpArgs<T>& a, hipStream_t s) {
     b.nblocks = b.tiles_x * b.tiles_y * (uint32_t)a.g.B;
     b.reverse = km_traversal_next(s);
     b.stream_out = km_stream_stores((uint64_t)a.g.B * a.g.C * a.g.h * a.g.w * sizeof(T));
-    uint32_t grid = b.nblocks;
-    if (KMB_PERSISTENT) {
-        // (a multiple of 8: a launch block and its logical blocks then share an XCD)
-        const uint32_t resident = (uint32_t)(km_device_cus() > 0 ? km_device_cus() : 1) * KMB_WAVES_PER_EU;
-        if (grid > resident) grid = resident;
-    }
+    const uint32_t grid = b.nblocks;
     if (a.g.align) {
         if (b.stream_out) hipLaunchKernelGGL((km_warp_fwd_box_kernel<T, CM, NC, 1, true>), dim3(grid), dim3(256), 0, s, b);
         else hipLaunchKernelGGL((km_warp_fwd_box_kernel<T, CM, NC, 1, false>), dim3(grid), dim3(256), 0, s, b);

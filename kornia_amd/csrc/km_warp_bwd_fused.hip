@@ -11,15 +11,21 @@
 //   * the matrix gradient is linear in the tap values: dL/dM = sum_q J_q^T sum_taps dw_tap/d(x,y) * src[tap] * grad_out[q].
 //     Every tap belongs to exactly one tile, so each owner adds the terms of the taps IT owns - the same ownership rule that
 //     makes the scatter add every contribution to grad_src exactly once;
-//   * the owner keeps its 64 x 64 x C source tile in LDS next to the 64 x 64 x C fixed-point accumulators (96 KB of the CU's
-//     160 KB): all tap reads are ds_read, no gathers, no texture-address traffic beyond the two coalesced streams;
-//   * one workgroup per CU, PERSISTENT, walking runs of horizontally adjacent tiles.  Everything a tile needs from HBM - the
-//     box of grad_out pixels that can touch it (KMO_SLOTS pixels per thread) and its source tile - is requested one tile
-//     AHEAD into registers: the source tile when the previous tile's scatter starts, the grad_out pixels slot by slot as the
-//     previous tile's slots are consumed (one register set holds both tiles).  The loads of tile k + 1 fly while tile k is
-//     scattered and the flush of tile k drains while tile k + 1 starts: the memory pipe of the CU never waits for a phase;
+//   * the owner keeps its 64 x 64 x C source tile in LDS next to the 64 x 64 x C fixed-point accumulators: all tap reads are
+//     ds_read, no gathers, no texture-address traffic beyond the two coalesced streams.  There are TWO source buffers (tile q uses
+//     buffer q & 1): accumulators + 2 source tiles are 144 KB of the CU's 160 KB for RGB;
+//   * one workgroup of 1 024 threads per CU, PERSISTENT, walking runs of horizontally adjacent tiles.  Everything a tile needs from
+//     HBM is requested one tile AHEAD, after the first slot of the previous tile's scatter: the box of grad_out pixels that can
+//     touch it into registers, slot by slot as the previous tile's slots are consumed (KMO_SLOTS pixels per thread; one register
+//     set holds both tiles), and its source tile - fp32 storage by LDS-DMA straight into the other source buffer (kmo_dma_src),
+//     16-bit storage through registers (kmo_issue_src, stored to LDS by the next tile's stage: kmo_store_src).  The loads of tile
+//     k + 1 fly while tile k is scattered and the flush of tile k drains while tile k + 1 starts: the memory pipe never waits for a phase;
+//   * the box is walked with a FIXED column per thread (KmoWalk): slot s of a thread is the pixel s slabs of whole rows further down;
+//   * a pixel's taps go one at a time, a tap's source reads in front of its LDS atomics (kmo_pix), one pixel between two scheduling fences;
 //   * because the whole box is in registers before the first contribution is added, the fixed-point scale comes from the
-//     EXACT maximum of |grad_out| over the box: no speculation, no redo pass, 3 more bits than km_warp_bwd_tiled.hip;
+//     EXACT maximum of |grad_out| over the box (one LDS atomic word per work item): no speculation, no redo pass, 3 more bits than
+//     km_warp_bwd_tiled.hip;
+//   * the tiles are described (every block-uniform field of KmoTile) by wave 0, KMO_RUN tiles at a time in its lanes, into a ring in LDS;
 //   * barriers inside the tile loop wait for LDS only (KM_LDS_BARRIER): a __syncthreads() would drain the loads in flight.
 //
 // Three launches, so that the persistent loop carries nothing it rarely needs (inlined, the general path and the box computation cost
@@ -38,6 +44,10 @@
 // is a slot with a load in flight the compiler waits for that load - in the middle of the scatter.  What the tile loop looks like is
 // shaped by where the compiler's waits land (it cannot count loads issued under a branch, and it orders every write of a register
 // after the loads in flight): see the comments at kmo_stage, kmo_issue_src and kmo_process.
+//
+// History.  Rounds 3 - 6 left their measured alternatives behind as compile-time switches (a linear-list walk of the box, other orders of
+// the tap reads, workspace records in the ring, the source tile through registers for fp32, two workgroups per CU, ablation builds ...).
+// They lost, their numbers are in profiles/ and DESIGN.md 4.6 / 12, and the last commit that still builds them is a903246.
 #include <stdlib.h>
 
 #include <atomic>
@@ -67,60 +77,13 @@ __device__ unsigned long long kmo_prof_rt[512 * 4];  // per worker: start, end o
 #define KMO_PROF_ARGS
 #endif
 
-#ifndef KMO_ABL
-#define KMO_ABL 0  // timing experiments only (wrong results): 1 no matrix-gradient work, 2 no LDS atomics, 4 no per-pixel work; round 6 - what the phases OUTSIDE the
-                   // scatter cost when they are simply gone (the upper bound of overlapping them): 8 no flush, 16 no image-end sums, 32 no barrier B1, 64 no barrier B2,
-                   // 128 no maximum of |grad_out| in the stage (profiles/r06/run6_*)
-#endif
-#ifndef KMO_NT
 #define KMO_NT 1024        // threads per workgroup (one workgroup per CU: 16 waves)
-#endif
 #define KMO_NW (KMO_NT / 64)
-#ifndef KMO_SLOTS
 #define KMO_SLOTS 6        // grad_out pixels per thread held in registers: boxes up to KMO_NT * KMO_SLOTS pixels are "regular"
-#endif
-#ifndef KMO_TH
 #define KMO_TH 64          // tile height (the tile width is KMT_TW = 64: the flush maps 16 lanes to a 256-byte row)
-#endif
 #define KMO_PLANE (KMO_TH * KMT_TW)
-#ifndef KMO_WG_PER_CU
-#define KMO_WG_PER_CU 1    // persistent workgroups per CU (what the LDS of a workgroup allows)
-#endif
-#ifndef KMO_REC_FIELDS
-#define KMO_REC_FIELDS 1   // tile coordinates and walk steps of a tile from its workspace record instead of integer divisions in the tile loop
-#endif
-#ifndef KMO_GM_LDS
-#define KMO_GM_LDS 1       // image-end sums of the matrix gradient through the (dead) source tile in LDS instead of nine wave reductions per wave
-#endif
-#ifndef KMO_RING_DESC
-#define KMO_RING_DESC 1    // the LDS ring holds DESCRIBED tiles (wave 0 derives every block-uniform field once per 64 tiles, lane = tile) instead of workspace records
-#endif
-#ifndef KMO_RED_ATOMIC
-#define KMO_RED_ATOMIC 1   // the maximum of |grad_out| over a pass through one LDS atomic word (two, alternating) instead of 16 wave partials read back by every wave
-#endif
-#ifndef KMO_FLUSH_STRAIGHT
-#define KMO_FLUSH_STRAIGHT 1  // full tiles: the flush's three accumulator reads in flight together (one LDS round trip instead of three)
-#endif
-#ifndef KMO_SRC_AT
-#define KMO_SRC_AT 0       // slot of the scatter after which the next tile's source tile is requested
-#endif
-#ifndef KMO_SRC_DMA
-#define KMO_SRC_DMA 1      // fp32 storage: the next tile's source tile by LDS-DMA (global_load_lds) into a SECOND source buffer instead of through registers
-#endif
-#ifndef KMO_TAB_AHEAD
-#define KMO_TAB_AHEAD 0    // the coordinate-table entries of a slot read one slot ahead of its arithmetic
-#endif
-#ifndef KMO_WALK_COLS
-#define KMO_WALK_COLS 1    // the box is walked with a FIXED column per thread (thread = (row tid / bw, column tid % bw) of a slab of KMO_NT / bw rows; slot s is the pixel s slabs below): see KmoWalk
-#endif
-#ifndef KMO_READS_FIRST
-#define KMO_READS_FIRST 1  // 1: tap by tap, a tap's three source reads in front of its three atomics (step 1.4395 -> 1.4364 ms, op 0.554 -> 0.545: profiles/r06/run18_*); 0: interleaved atomic, read, atomic, read, ...; 2: ALL twelve reads of a pixel in front of all its atomics, unconditional - measured 9 % SLOWER (op 0.593 against 0.545, run19: every pixel then issues the reads of taps it does not own)
-#endif
-#ifndef KMO_FENCE_EVERY
-#define KMO_FENCE_EVERY 1  // slots of the scatter between two scheduling fences (1: one pixel at a time)
-#endif
-#define KMO_RUN (KMO_SRC_DMA ? 16 : 64)  // records wave 0 fetches from the workspace at once (lane = tile), into alternating halves of a 2 x KMO_RUN ring (the second source buffer takes 48 KB of the ring's CU)
-#define KMO_RING_INTS (KMO_RING_DESC ? 32 : 20)  // ints per tile in the LDS ring
+#define KMO_RUN 16         // tiles wave 0 describes at once (lane = tile), into alternating halves of a 2 x KMO_RUN ring in LDS
+#define KMO_RING_INTS 32   // ints per described tile in the ring (kmo_fetch_boxes / kmo_load_desc)
 #define KMO_BOX_INTS 20    // workspace record of a tile: j0, j1, i0, i1, head-room bits, flags, first plane, matrix row, the 9 matrix entries, tile (tx, ty), (image, group), walk steps
 enum { KMO_F_FIXED = 1, KMO_F_REGULAR = 4, KMO_F_NONFINITE = 8 };
 
@@ -149,7 +112,7 @@ struct KmWarpFusedArgs {
 };
 
 __host__ __device__ constexpr int kmo_lds_bytes(int cc) {
-    return (KMT_BAND_W + KMT_TAB) * 16 + (KMO_SRC_DMA ? 3 : 2) * cc * KMO_PLANE * 4 + 2 * KMO_RUN * KMO_RING_INTS * 4 + KMO_NW * 8 + KMO_NW * 9 * 8;
+    return (KMT_BAND_W + KMT_TAB) * 16 + 3 * cc * KMO_PLANE * 4 + 2 * KMO_RUN * KMO_RING_INTS * 4 + KMO_NW * 8 + KMO_NW * 9 * 8;
 }
 
 // One tile (everything block-uniform)
@@ -160,10 +123,17 @@ struct KmoTile {
     int j0, j1, i0, i1, hb;
     bool fixed_ok, regular, svec, fvec;
     int bw, nq;
-    int di, dj;        // row / column step of the linear walk over the box (KMO_NT / bw, KMO_NT % bw)
-    int p, npass;      // the box is walked in npass passes of KMO_CAP pixels; this work item is pass p
+    int di, dj;        // KMO_NT / bw: whole rows of the box in a slab of the walk (KmoWalk); KMO_NT % bw (kept in the record, not used by the walk)
+    int p, npass;      // the box is walked in npass passes of KMO_SLOTS slabs; this work item is pass p
 };
-#define KMO_CAP (KMO_NT * KMO_SLOTS)  // pixels of a box the registers of a workgroup hold
+
+// fp32 storage: the source tiles arrive by LDS-DMA, double-buffered (kmo_dma_src); 16-bit storage: through registers (kmo_issue_src / kmo_store_src)
+template <typename T>
+constexpr bool kmo_dma = sizeof(T) == 4;
+// the image-end sums of the matrix gradient go through the (dead) source tile in LDS when it has room for nine partials per thread (RGB);
+// otherwise (grey) nine wave reductions per wave
+template <int CC>
+constexpr bool kmo_gm_lds = CC * KMO_PLANE >= 9 * KMO_NT;
 
 template <typename T>
 __device__ __forceinline__ void kmo_tile_coords(const KmWarpFusedArgs<T>& a, uint32_t t, int& b, int& tx, int& ty) {
@@ -223,10 +193,9 @@ __global__ __launch_bounds__(256) void km_warp_bwd_boxes_kernel(const KmWarpFuse
     const int bwc = max(bw, 1);
     o[17] = tx | (ty << 16);                               // tile column / row (< 2^16 each: checked by the host)
     o[18] = bg;                                            // (image, channel group) index of the sequence
-    o[19] = (KMO_NT / bwc) | ((KMO_NT % bwc) << 16);       // row / column step of the linear walk over the box, KMO_NT pixels apart
+    o[19] = (KMO_NT / bwc) | ((KMO_NT % bwc) << 16);       // whole rows of the box that KMO_NT threads cover (a slab of the walk), and the remainder
 }
 
-// tile t from its (block-uniform) workspace record
 // the matrix of a tile from its record (block-uniform values in vector registers: what the caller does not use costs nothing)
 __device__ __forceinline__ void kmo_matrix(const int* rec, float (&m)[9]) {
 #pragma unroll
@@ -235,7 +204,7 @@ __device__ __forceinline__ void kmo_matrix(const int* rec, float (&m)[9]) {
 // record of the q-th tile of this worker in the LDS ring
 __device__ __forceinline__ const int* kmo_ring(const int* s_box, uint32_t q) { return s_box + (q % (2u * KMO_RUN)) * KMO_RING_INTS; }
 
-// U: the record is block-uniform (read through LDS / scalar registers); !U: one record per lane (kmo_fetch_boxes)
+// tile t from its workspace record.  U: the record is block-uniform (the general launch); !U: one record per lane (kmo_fetch_boxes)
 template <typename T, bool U = true>
 __device__ __forceinline__ void kmo_describe(const KmWarpFusedArgs<T>& a, int t, const int* rec, KmoTile& d) {
     const KmWarpGeom<float>& g = a.g;
@@ -244,7 +213,6 @@ __device__ __forceinline__ void kmo_describe(const KmWarpFusedArgs<T>& a, int t,
     d.t = t;
     if (t < 0) return;
     int tx, ty;
-#if KMO_REC_FIELDS
     {
         const int txy = un(rec[17]);
         tx = txy & 0xffff; ty = (int)((uint32_t)txy >> 16);
@@ -252,9 +220,6 @@ __device__ __forceinline__ void kmo_describe(const KmWarpFusedArgs<T>& a, int t,
         const int st = un(rec[19]);
         d.di = st & 0xffff; d.dj = (int)((uint32_t)st >> 16);
     }
-#else
-    kmo_tile_coords(a, (uint32_t)t, d.b, tx, ty);
-#endif
     d.X0 = tx * KMT_TW; d.Y0 = ty * KMO_TH;
     d.TWc = min(d.X0 + KMT_TW, g.W) - d.X0; d.THc = min(d.Y0 + KMO_TH, g.H) - d.Y0;
     d.j0 = un(rec[0]); d.j1 = un(rec[1]); d.i0 = un(rec[2]); d.i1 = un(rec[3]);
@@ -264,31 +229,25 @@ __device__ __forceinline__ void kmo_describe(const KmWarpFusedArgs<T>& a, int t,
     d.fixed_ok = (fl & KMO_F_FIXED) != 0; d.regular = (fl & KMO_F_REGULAR) != 0;
     const int bw = d.j1 - d.j0 + 1, bh = d.i1 - d.i0 + 1;
     d.bw = bw;
-#if !KMO_REC_FIELDS
-    d.di = un(KMO_NT / max(bw, 1)); d.dj = un(KMO_NT % max(bw, 1));
-#endif
     d.nq = (bw > 0 && bh > 0) ? bw * bh : 0;
     d.p = 0;
-#if KMO_WALK_COLS
     d.npass = d.regular ? max(1, (bh + KMO_SLOTS * max(d.di, 1) - 1) / (KMO_SLOTS * max(d.di, 1))) : 1;  // (a pass = KMO_SLOTS slabs of di rows)
-#else
-    d.npass = d.regular ? max(1, (d.nq + KMO_CAP - 1) / KMO_CAP) : 1;  // (a tile of the general launch is ONE item of the persistent loop, whatever its box)
-#endif
     // 16-byte rows of the source tile / of the tile flush
     d.svec = (sizeof(T) == 4) && d.TWc == KMT_TW && (g.W & 3) == 0 && ((uintptr_t)a.src & 15) == 0;
     d.fvec = d.TWc == KMT_TW && (g.W & 3) == 0 && ((uintptr_t)a.gsrc & 15) == 0;
 }
 
-// records of tiles q0 .. q0 + 63 of this worker, workspace -> LDS, one lane per tile (wave 0)
+// tiles q0 .. q0 + KMO_RUN - 1 of this worker, workspace record -> described tile in the LDS ring, one lane per tile (wave 0)
 template <typename T>
 __device__ __forceinline__ void kmo_fetch_boxes(const KmWarpFusedArgs<T>& a, uint32_t q0, int lane, int* s_box) {
     if (lane >= KMO_RUN) return;  // (lane = tile of the run)
     const int t = kmo_tile_of(a, q0 + (uint32_t)lane);
-    static_assert(KMO_BOX_INTS % 4 == 0 && KMO_RING_INTS % 4 == 0 && KMO_RUN <= 64, "16-byte pieces; one lane per tile of a run");
+    static_assert(KMO_BOX_INTS % 4 == 0 && KMO_RING_INTS % 4 == 0, "records and ring entries are moved in 16-byte pieces");
+    static_assert(KMO_RUN <= 64, "one lane of wave 0 per tile of a run");
+    static_assert(KMO_RING_INTS >= 7 * 4, "a described tile is seven 16-byte pieces");
     int4* dst = reinterpret_cast<int4*>(s_box) + (KMO_RING_INTS / 4) * (((q0 / KMO_RUN) & 1u) * KMO_RUN + (uint32_t)lane);
-#if KMO_RING_DESC
     // The description of a tile is ~150 scalar instructions (and three LDS round trips) that all 16 waves of the workgroup executed for
-    // every tile, between the barrier and the scatter: here wave 0 derives it once, 64 tiles at a time in its vector lanes, and the
+    // every tile, between the barrier and the scatter: here wave 0 derives it once, KMO_RUN tiles at a time in its vector lanes, and the
     // tile loop reads the finished fields (kmo_load_desc).  Entries 8 .. 16 are the matrix, where kmo_matrix expects it.
     KmoTile d;
     const int* rec = a.ws + (size_t)max(t, 0) * KMO_BOX_INTS;
@@ -303,19 +262,8 @@ __device__ __forceinline__ void kmo_fetch_boxes(const KmWarpFusedArgs<T>& a, uin
     dst[4] = make_int4(mq[2].x, d.X0, d.Y0, d.TWc);
     dst[5] = make_int4(d.THc, d.bw, d.nq, d.di);
     dst[6] = make_int4(d.dj, d.npass, d.b, d.j1);
-#else
-    if (t >= 0) {
-        const int4* rec = reinterpret_cast<const int4*>(a.ws + (size_t)t * KMO_BOX_INTS);
-#pragma unroll 1
-        for (int k = 0; k < KMO_BOX_INTS / 4; ++k) dst[k] = rec[k];
-    } else {
-        dst[0] = make_int4(0, -1, 0, -1);
-        dst[1] = make_int4(0, 0, 0, 0);
-    }
-#endif
 }
 
-#if KMO_RING_DESC
 // the described tile at r (kmo_fetch_boxes) -> block-uniform registers: seven 16-byte LDS reads in flight together, no arithmetic
 __device__ __forceinline__ void kmo_load_desc(const int* r, KmoTile& d) {
     const int4* p = reinterpret_cast<const int4*>(r);
@@ -330,9 +278,8 @@ __device__ __forceinline__ void kmo_load_desc(const int* r, KmoTile& d) {
     d.dj = kmt_uniform(a6.x); d.npass = kmt_uniform(a6.y); d.b = kmt_uniform(a6.z); d.j1 = kmt_uniform(a6.w);
     d.p = 0;
 }
-#endif
 
-// first pixel of this thread in a box of width bw walked as a linear list (element e = tid; tid < 2^24: the float quotient is off by at most one)
+// (row, column) of element `tid` of a box of width bw taken row by row (tid < 2^24: the float quotient is off by at most one)
 __device__ __forceinline__ void kmo_first(int tid, int bw, int& qi, int& qj) {  // tid: element index (< 2^24)
     // (a reciprocal, not a division: 15 instructions fewer per thread and tile; the two corrections below absorb its error)
     qi = (int)(((float)tid + 0.5f) * kmt_uniform(__builtin_amdgcn_rcpf((float)bw)));
@@ -403,7 +350,7 @@ __device__ __forceinline__ void kmo_store_src(const KmoTile& d, const float (&S)
     }
 }
 
-// fp32 storage (KMO_SRC_DMA): the same pieces of the source tile, every lane's straight into LDS (KM_GLDS16: the wave's 64 pieces land at
+// fp32 storage (kmo_dma): the same pieces of the source tile, every lane's straight into LDS (KM_GLDS16: the wave's 64 pieces land at
 // consecutive 16-byte cells from a wave-uniform base - exactly kmo_store_src's layout, idx4 = k * KMO_NT + tid).  No register holds the tile
 // on its way, no ds_write: what kmo_issue_src + kmo_store_src do in two phases a tile apart is ONE request here, and the 12 registers of S
 // are free during the scatter.  Ragged / unaligned tiles: one float per lane (a tile row per wave instruction), the same clamped addresses.
@@ -484,95 +431,33 @@ __device__ __forceinline__ void kmo_pix(const KmtPix& q, const float (&go)[CC], 
     }
     // scale = 2^k: (wx * wy) * scale == wx * (wy * scale) bit for bit.  Tap-outer order: one exec-mask region per tap (the four taps
     // without exec-mask regions - zero weights, non-owned taps parked on a cell of the lane's own - and a wave-uniform skip of pixels that
-    // own no tap measured the same time: profiles/r04/bwd_fused_per_pixel_variants.txt.  That was the linear walk, where a whole wave rarely
-    // owned nothing; waves without a VALID lane - the column walk has them in every box's last slab - never get here: kmo_process).
+    // own no tap measured the same time: profiles/r04/bwd_fused_per_pixel_variants.txt.  Waves without a VALID lane - every box has them
+    // in its last slab - never get here: kmo_process).
     const float wy0s = FIXED ? t.wy0 * scale : t.wy0, wy1s = FIXED ? t.wy1 * scale : t.wy1;
     const float w00 = t.wx1 * wy1s, w01 = t.wx0 * wy1s, w10 = t.wx1 * wy0s, w11 = t.wx0 * wy0s;
     float gix = 0.f, giy = 0.f;
     const int l00 = (int)(uy * (uint32_t)KMT_TW + ux);
-#if KMO_READS_FIRST == 2
-    if (FIXED) {
-        // ALL twelve source reads of the pixel in front of ALL its atomics, unconditional (a tap another tile owns reads the plane's first cell and
-        // its product is dropped): LDS operations of a wave complete in order, so the pixel's critical path - position -> source values -> terms -
-        // waits for ONE round trip, not for four that each queue behind the previous tap's atomics.  The sums are the same fma chains in the same
-        // order (a dropped tap adds +-w * 0 = 0 to a finite sum: FIXED tiles have finite positions).
-        const int b00 = t00 ? l00 : 0, b01 = t01 ? l00 : -1, b10 = t10 ? l00 : -KMT_TW, b11 = t11 ? l00 : -(KMT_TW + 1);
-        float sv_[4][CC];
-#pragma unroll
-        for (int c = 0; c < CC; ++c) {
-            sv_[0][c] = (KMO_ABL & 1) ? 0.f : s_src[b00 + c * KMO_PLANE];
-            sv_[1][c] = (KMO_ABL & 1) ? 0.f : s_src[b01 + c * KMO_PLANE + 1];
-            sv_[2][c] = (KMO_ABL & 1) ? 0.f : s_src[b10 + c * KMO_PLANE + KMT_TW];
-            sv_[3][c] = (KMO_ABL & 1) ? 0.f : s_src[b11 + c * KMO_PLANE + KMT_TW + 1];
-        }
-#define KMO_TAP_ADD(pred, OFF, W)                                                                                     \
-        if ((pred) && !(KMO_ABL & 2)) {                                                                               \
-            _Pragma("unroll") for (int c = 0; c < CC; ++c) atomicAdd(s_acc + l00 + c * KMO_PLANE + (OFF), kmt_quant((W) * go[c])); \
-        }
-        KMO_TAP_ADD(t00, 0, w00)
-        KMO_TAP_ADD(t01, 1, w01)
-        KMO_TAP_ADD(t10, KMT_TW, w10)
-        KMO_TAP_ADD(t11, KMT_TW + 1, w11)
-#undef KMO_TAP_ADD
-        float dot_[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float d = 0.f;
-#pragma unroll
-            for (int c = 0; c < CC; ++c) d = (c == 0) ? go[c] * sv_[k][c] : km_fma(go[c], sv_[k][c], d);
-            dot_[k] = d;
-        }
-        dot_[0] = t00 ? dot_[0] : 0.f; dot_[1] = t01 ? dot_[1] : 0.f; dot_[2] = t10 ? dot_[2] : 0.f; dot_[3] = t11 ? dot_[3] : 0.f;
-        gix = km_fma(-t.wy1, dot_[0], gix); giy = km_fma(-t.wx1, dot_[0], giy);
-        gix = km_fma(+t.wy1, dot_[1], gix); giy = km_fma(-t.wx0, dot_[1], giy);
-        gix = km_fma(-t.wy0, dot_[2], gix); giy = km_fma(+t.wx1, dot_[2], giy);
-        gix = km_fma(+t.wy0, dot_[3], gix); giy = km_fma(+t.wx0, dot_[3], giy);
-    } else {
-#endif
-#if KMO_READS_FIRST
     // the tap's source values are REQUESTED IN FRONT of its atomics: LDS operations of a wave complete in order, so a read queued behind the
-    // atomics waits for them as well - and the wait for the reads is on the wave's critical path (position -> taps -> terms), the atomics are not
+    // atomics waits for them as well - and the wait for the reads is on the wave's critical path (position -> taps -> terms), the atomics are not.
+    // (ALL twelve reads of the pixel in front of all its atomics, unconditional, measured 9 % slower: every pixel then reads taps it does not own.)
 #define KMO_TAP(pred, OFF, W, SX, WX, SY, WY)                                                        \
     if (pred) {                                                                                       \
         float sv_[CC];                                                                                \
-        _Pragma("unroll") for (int c = 0; c < CC; ++c) sv_[c] = (KMO_ABL & 1) ? 0.f : s_src[l00 + c * KMO_PLANE + (OFF)]; \
+        _Pragma("unroll") for (int c = 0; c < CC; ++c) sv_[c] = s_src[l00 + c * KMO_PLANE + (OFF)];   \
         _Pragma("unroll") for (int c = 0; c < CC; ++c) {                                              \
-            if (!(KMO_ABL & 2)) {                                                                     \
-                if (FIXED) atomicAdd(s_acc + l00 + c * KMO_PLANE + (OFF), kmt_quant((W) * go[c]));    \
-                else atomicAdd((float*)s_acc + l00 + c * KMO_PLANE + (OFF), (W) * go[c]);             \
-            }                                                                                         \
+            if (FIXED) atomicAdd(s_acc + l00 + c * KMO_PLANE + (OFF), kmt_quant((W) * go[c]));        \
+            else atomicAdd((float*)s_acc + l00 + c * KMO_PLANE + (OFF), (W) * go[c]);                 \
         }                                                                                             \
         float dot = 0.f;                                                                              \
         _Pragma("unroll") for (int c = 0; c < CC; ++c) dot = (c == 0) ? go[c] * sv_[c] : km_fma(go[c], sv_[c], dot); \
         gix = km_fma(SX (WX), dot, gix);                                                              \
         giy = km_fma(SY (WY), dot, giy);                                                              \
     }
-#else
-#define KMO_TAP(pred, OFF, W, SX, WX, SY, WY)                                                        \
-    if (pred) {                                                                                       \
-        float dot = 0.f;                                                                              \
-        _Pragma("unroll") for (int c = 0; c < CC; ++c) {                                              \
-            if (!(KMO_ABL & 2)) {                                                                     \
-                if (FIXED) atomicAdd(s_acc + l00 + c * KMO_PLANE + (OFF), kmt_quant((W) * go[c]));    \
-                else atomicAdd((float*)s_acc + l00 + c * KMO_PLANE + (OFF), (W) * go[c]);             \
-            }                                                                                         \
-            if (!(KMO_ABL & 1)) {                                                                     \
-                const float sv = s_src[l00 + c * KMO_PLANE + (OFF)];                                  \
-                dot = (c == 0) ? go[c] * sv : km_fma(go[c], sv, dot);                                 \
-            }                                                                                         \
-        }                                                                                             \
-        gix = km_fma(SX (WX), dot, gix);                                                              \
-        giy = km_fma(SY (WY), dot, giy);                                                              \
-    }
-#endif
     KMO_TAP(t00, 0, w00, -, t.wy1, -, t.wx1)
     KMO_TAP(t01, 1, w01, +, t.wy1, -, t.wx0)
     KMO_TAP(t10, KMT_TW, w10, -, t.wy0, +, t.wx1)
     KMO_TAP(t11, KMT_TW + 1, w11, +, t.wy0, +, t.wx0)
 #undef KMO_TAP
-#if KMO_READS_FIRST == 2
-    }
-#endif
     // this tile's share of the pixel's terms (zero when it owns none of the taps: no 0 * inf from a degenerate position)
     const bool any = t00 | t01 | t10 | t11;
     float ax, ay, az;
@@ -587,37 +472,26 @@ struct KmoConsts {
     float Wm1, Hm1, hW, hH, mx, my;
 };
 
-// Walk of a box.
-// KMO_WALK_COLS (round 6): thread tid sits at (row tid / bw, column tid % bw) of a SLAB of P = KMO_NT / bw whole rows of the box (threads beyond
+// Walk of a box: thread tid sits at (row tid / bw, column tid % bw) of a SLAB of P = KMO_NT / bw whole rows of the box (threads beyond
 // P * bw idle: 44 of 1 024 on a 70-column box) and slot s is the pixel s slabs further down, in the SAME column.  Nothing of the walk is per-lane
 // arithmetic any more: the column-table entry is read once per tile, the row index and the element offset advance by block-uniform steps (P,
-// P * w), a slot is valid while s P + row < rows of the pass.  The linear list it replaces (element e = s * KMO_NT + tid, both coordinates
-// advanced with carry for the current AND the next tile's box, a 32-bit multiply per request) was 29 of the 151 vector issue slots of a
-// visited pixel; a 70 x 70 box is 5 slabs of 14 rows = 80 wave-slots where the list had 77.  A pass of a box larger than the registers hold
-// is KMO_SLOTS slabs.
-// Otherwise: a linear list of pixels, KMO_NT apart: element e = s * KMO_NT + tid sits at (qi, qj) of the box
+// P * w), a slot is valid while s P + row < rows of the pass.  A pass of a box larger than the registers hold is KMO_SLOTS slabs.
+// (Until round 6 the box was a linear list, element e = s * KMO_NT + tid, both coordinates advanced with carry per request: 29 of the 151
+// vector issue slots of a visited pixel.  A 70 x 70 box is 5 slabs of 14 rows = 80 wave-slots where the list had 77.)
 struct KmoWalk {
-#if KMO_WALK_COLS
     int trow;       // this thread's row in a slab (0x10000 for the idle threads beyond the slab)
     int nrows;      // rows of this pass (0: nothing to request)
     int P;          // rows of a slab
     uint32_t off;   // element offset of this thread's slot-0 pixel in a grad_out plane
     uint32_t step;  // ... from one slot to the next: P * w
-#else
-    int qi, qj, di, dj, bw, nq;
-    uint32_t row0;  // element offset of the box's first pixel in a grad_out plane
-#endif
 };
-#if KMO_WALK_COLS
 // rows of pass d.p of a regular tile's box
 __device__ __forceinline__ int kmo_pass_rows(const KmoTile& d) {
     const int P = max(d.di, 1);
     return (d.regular && d.nq > 0) ? min((d.i1 - d.i0 + 1) - d.p * KMO_SLOTS * P, KMO_SLOTS * P) : 0;
 }
-#endif
 template <typename T>
 __device__ __forceinline__ void kmo_walk_init(const KmWarpFusedArgs<T>& a, const KmoTile& d, KmoWalk& wk) {
-#if KMO_WALK_COLS
     const int P = max(d.di, 1);
     int trow, tcol;
     kmo_first((int)threadIdx.x, max(d.bw, 1), trow, tcol);
@@ -626,55 +500,32 @@ __device__ __forceinline__ void kmo_walk_init(const KmWarpFusedArgs<T>& a, const
     wk.off = (uint32_t)(d.i0 + d.p * KMO_SLOTS * P + trow) * (uint32_t)a.g.w + (uint32_t)(d.j0 + tcol);
     wk.trow = trow < P ? trow : 0x10000;
     wk.step = (uint32_t)P * (uint32_t)a.g.w;
-#else
-    wk.bw = max(d.bw, 1);
-    wk.nq = d.regular ? min(d.nq - d.p * KMO_CAP, KMO_CAP) : 0;  // pixels of this pass (a tile of the general path loads its pixels itself)
-    wk.di = d.di;
-    wk.dj = d.dj;
-    kmo_first(d.p * KMO_CAP + (int)threadIdx.x, wk.bw, wk.qi, wk.qj);
-    wk.row0 = (uint32_t)d.i0 * (uint32_t)a.g.w + (uint32_t)d.j0;
-#endif
 }
 __device__ __forceinline__ void kmo_walk_none(KmoWalk& wk) {  // nothing to request (the end of the sequence, a tile of the general launch)
-#if KMO_WALK_COLS
     wk.nrows = 0;
-#else
-    wk.nq = 0;
-#endif
 }
-// request slot s of the walk's tile (zeros beyond the end of the box) and advance
+// request slot s of the walk's tile (zeros beyond the end of the box)
 template <typename T, int CC>
-__device__ __forceinline__ void kmo_request_slot(const T* gout_b, size_t dst_plane, int w, int s, KmoWalk& wk, float (&Gs)[CC]) {
+__device__ __forceinline__ void kmo_request_slot(const T* gout_b, size_t dst_plane, int s, const KmoWalk& wk, float (&Gs)[CC]) {
     const T* gout_c[CC];  // (one base and the plane size are kept; the channels' pointers are formed at the request)
 #pragma unroll
     for (int c = 0; c < CC; ++c) gout_c[c] = gout_b + (size_t)c * dst_plane;
-#if KMO_WALK_COLS
-    (void)w;
     const bool valid = wk.trow < wk.nrows - s * wk.P;
 #pragma unroll
     for (int c = 0; c < CC; ++c) Gs[c] = 0.f;
     if (valid) kmt_load_go<T, CC>(gout_c, wk.off + (uint32_t)s * wk.step, Gs);
-#else
-    const bool valid = s * KMO_NT + (int)threadIdx.x < wk.nq;
-#pragma unroll
-    for (int c = 0; c < CC; ++c) Gs[c] = 0.f;
-    if (valid) kmt_load_go<T, CC>(gout_c, wk.row0 + (uint32_t)wk.qi * (uint32_t)w + (uint32_t)wk.qj, Gs);
-    kmt_advance(wk.qi, wk.qj, wk.di, wk.dj, wk.bw);
-#endif
 }
 
-// The pixels a thread holds in registers (regular tiles): element e = s * KMO_NT + tid of the box walked as a linear list.  As soon
+// The pixels a thread holds in registers (regular tiles): slot s is its column's pixel in slab s of the pass (KmoWalk).  As soon
 // as slot s has been consumed its registers are REFILLED with slot s of the next tile (wn, gout_n): one register set holds both tiles,
 // and the next tile's requests are spread over the whole scatter instead of issued in one burst.
 template <typename T, int CM, int ALIGN, int CC, bool FAST, bool FIXED, int PADX>
 __device__ __forceinline__ void kmo_process(const float (&m)[9], const KmoTile& d, const KmoConsts& k, float (&G)[KMO_SLOTS][CC], const float4* s_u4,
-                                            const float4* s_v4, int* s_acc, const float* s_src, float scale, float (&A)[9], int w, KmoWalk& wn,
+                                            const float4* s_v4, int* s_acc, const float* s_src, float scale, float (&A)[9], const KmoWalk& wn,
                                             const T* gout_n, size_t dst_plane, bool mine, const KmWarpFusedArgs<T>& a, const KmoTile& nxt,
                                             float (&S)[CC * KMO_PLANE / KMO_NT], float* s_src_next) {
     const int tid = threadIdx.x;
     const int bw = max(d.bw, 1);
-#if KMO_WALK_COLS
-    static_assert(!KMO_TAB_AHEAD, "KMO_TAB_AHEAD belongs to the linear walk");
     const int P = max(d.di, 1);
     const int nrows = kmo_pass_rows(d);  // rows of this pass
     int trow, tcol;
@@ -684,7 +535,9 @@ __device__ __forceinline__ void kmo_process(const float (&m)[9], const KmoTile& 
     const float4 c0 = s_u4[min(tcol, KMT_BAND_W - 1)];  // (the same column for every slot; a tile of the general launch may be wider than the table: nothing of it is used)
 #pragma unroll
     for (int s = 0; s < KMO_SLOTS; ++s) {
-        if (mine && s * P < nrows && !(KMO_ABL & 4)) {  // block-uniform
+        // (mine == false: a tile this launch leaves to the general one - only the refill below happens.  One code path for both, so
+        // that the compiler sees ONE set of registers for the slots: two paths meant copies, and a wait for every load in flight)
+        if (mine && s * P < nrows) {  // block-uniform
             const bool valid = trow < nrows - s * P;
             // A wave without a valid lane (the waves below the box's last row in its last slab: 9 of 16 in the fifth slab of a 66-row box) would
             // own no tap and add nine zeros to A - finite partials that start at +0 stay what they are - after the table read, both divisions,
@@ -697,59 +550,14 @@ __device__ __forceinline__ void kmo_process(const float (&m)[9], const KmoTile& 
                 kmo_pix<CM, CC, FAST, FIXED>(q, G[s], s_acc, s_src, scale, (uint32_t)d.TWc, (uint32_t)d.THc, c0.w, r0.w, PADX ? k.mx * gdx : k.mx, PADX ? k.my * gdy : k.my, A);
             }
         }
-#else
-    const int di = d.di, dj = d.dj;
-    const int nqp = min(d.nq - d.p * KMO_CAP, KMO_CAP);  // pixels of this pass
-    int qi, qj;
-    kmo_first(d.p * KMO_CAP + tid, bw, qi, qj);
-#if KMO_TAB_AHEAD
-    // the table entries of a slot are read ONE SLOT AHEAD - in front of the previous pixel's twelve LDS atomics and tap reads, which an LDS
-    // read issued behind them would queue behind (LDS operations of a wave complete in order)
-    float4 cN = make_float4(0.f, 0.f, 0.f, 0.f), rN = cN;
-    bool vN = false;
-    if (mine && 0 < nqp && !(KMO_ABL & 4)) {
-        vN = tid < nqp;
-        cN = s_u4[vN ? qj : 0]; rN = s_v4[vN ? qi : 0];
-        kmt_advance(qi, qj, di, dj, bw);
-    }
-#endif
-#pragma unroll
-    for (int s = 0; s < KMO_SLOTS; ++s) {
-        // (mine == false: a tile this launch leaves to the general one - only the refill below happens.  One code path for both, so
-        // that the compiler sees ONE set of registers for the slots: two paths meant copies, and a wait for every load in flight)
-        if (mine && s * KMO_NT < nqp && !(KMO_ABL & 4)) {  // block-uniform
-#if KMO_TAB_AHEAD
-            const bool valid = vN;
-            const float4 c0 = cN, r0 = rN;
-            if ((s + 1) * KMO_NT < nqp) {
-                vN = (s + 1) * KMO_NT + tid < nqp;
-                cN = s_u4[vN ? qj : 0]; rN = s_v4[vN ? qi : 0];
-                kmt_advance(qi, qj, di, dj, bw);
-            }
-#else
-            const bool valid = s * KMO_NT + tid < nqp;
-            const int vqi = valid ? qi : 0, vqj = valid ? qj : 0;
-            const float4 c0 = s_u4[vqj], r0 = s_v4[vqi];
-#endif
-            if (__ballot(valid) != 0ull) {  // (wave-uniform: the waves beyond the end of the list, see the column walk)
-                KmtPix q;
-                float gdx, gdy;
-                kmt_pix_position_pad<CM, ALIGN, FAST, PADX>(m, kmt_half(c0), kmt_half(r0), valid, k.Wm1, k.hW, k.Hm1, k.hH, (uint32_t)d.X0, (uint32_t)d.Y0, a.g.W, a.g.H, q, gdx, gdy);
-                kmo_pix<CM, CC, FAST, FIXED>(q, G[s], s_acc, s_src, scale, (uint32_t)d.TWc, (uint32_t)d.THc, c0.w, r0.w, PADX ? k.mx * gdx : k.mx, PADX ? k.my * gdy : k.my, A);
-            }
-#if !KMO_TAB_AHEAD
-            kmt_advance(qi, qj, di, dj, bw);
-#endif
-        }
-#endif
-        kmo_request_slot<T, CC>(gout_n, dst_plane, w, s, wn, G[s]);
-        // the next tile's source tile is requested here, not before the loop: registers that are live across the whole loop get
-        // moved by the register allocator at its entry, and a move of a register with a load in flight is a wait for that load
-        if (s == KMO_SRC_AT && nxt.t >= 0 && nxt.regular && nxt.p == 0) {
-            if constexpr (KMO_SRC_DMA && sizeof(T) == 4) kmo_dma_src<T, CC>(a, nxt, s_src_next);
+        kmo_request_slot<T, CC>(gout_n, dst_plane, s, wn, G[s]);
+        // the next tile's source tile is requested here, after slot 0, not before the loop: registers that are live across the whole loop
+        // get moved by the register allocator at its entry, and a move of a register with a load in flight is a wait for that load
+        if (s == 0 && nxt.t >= 0 && nxt.regular && nxt.p == 0) {
+            if constexpr (kmo_dma<T>) kmo_dma_src<T, CC>(a, nxt, s_src_next);
             else kmo_issue_src<T, CC>(a, nxt, S);
         }
-        if ((s + 1) % KMO_FENCE_EVERY == 0) KM_SCHED_FENCE();  // one pixel at a time: interleaving the slots costs more registers than it hides latency
+        KM_SCHED_FENCE();  // one pixel at a time: interleaving the slots costs more registers than it hides latency
     }
 }
 
@@ -902,13 +710,12 @@ __device__ __forceinline__ void kmo_general_tile(const KmWarpFusedArgs<T>& a, co
 // convert and write the tile, leaving the accumulators zeroed for the next one
 template <typename T, int CC>
 __device__ __forceinline__ void kmo_flush(const KmWarpFusedArgs<T>& a, const KmoTile& d, int* s_acc, bool finite, float inv_scale, bool discard = false) {
-    if (KMO_ABL & 8) return;
     const KmWarpGeom<float>& g = a.g;
     const int tid = threadIdx.x;
     const size_t src_plane = (size_t)g.H * g.W;
     float* gsrc_b = a.gsrc + (size_t)d.plane0 * src_plane;
-#if KMO_FLUSH_STRAIGHT
-    if (d.fvec && d.THc == KMO_TH && finite && KMO_TH * KMT_TW / 4 == KMO_NT) {
+    static_assert(KMO_TH * KMT_TW / 4 == KMO_NT, "the straight flush: one 16-byte piece of a plane per thread");
+    if (d.fvec && d.THc == KMO_TH && finite) {
         // a full tile: one 16-byte piece per thread and channel, the reads of all channels in flight together (- 1 % on the kernel:
         // profiles/r04/bwd_fused_latency_variants.txt, runs 34 and 38)
         int4 q[CC];
@@ -932,7 +739,6 @@ __device__ __forceinline__ void kmo_flush(const KmWarpFusedArgs<T>& a, const Kmo
         }
         return;
     }
-#endif
     if (d.fvec) {
         // full-width tile, 16-byte aligned rows: 16 lanes x 16 bytes cover a tile row, a wave writes 4 rows per store
         const int col4 = (tid & 15) * 4, row0 = tid >> 4;
@@ -980,7 +786,7 @@ struct KmoLds {
     float4 *s_u4, *s_v4;
     int* s_acc;
     float* s_src;
-    float* s_src2;   // KMO_SRC_DMA: the second source buffer (tile q uses buffer q & 1)
+    float* s_src2;   // the second source buffer (kmo_dma: tile q uses buffer q & 1)
     int* s_box;
     uint32_t* s_red;
     double* s_gm;
@@ -992,9 +798,9 @@ __device__ __forceinline__ KmoLds kmo_carve(char* smem_raw) {
     l.s_v4 = l.s_u4 + KMT_BAND_W;                           // [KMT_TAB] per row of the box
     l.s_acc = (int*)(l.s_v4 + KMT_TAB);                     // [CC][TH][TW] fixed-point accumulators
     l.s_src = (float*)(l.s_acc + CC * KMO_PLANE);           // [CC][TH][TW] the source tile (minus fill)
-    l.s_src2 = l.s_src + CC * KMO_PLANE;                    // [CC][TH][TW] (KMO_SRC_DMA only)
-    l.s_box = (int*)(l.s_src + (KMO_SRC_DMA ? 2 : 1) * CC * KMO_PLANE);  // [2 KMO_RUN][KMO_BOX_INTS] ring of records of this worker's tiles
-    l.s_red = (uint32_t*)(l.s_box + 2 * KMO_RUN * KMO_RING_INTS);  // [KMO_NW] (8-byte slots: keeps s_gm aligned)
+    l.s_src2 = l.s_src + CC * KMO_PLANE;                    // [CC][TH][TW] (used by fp32 storage only: kmo_dma)
+    l.s_box = (int*)(l.s_src2 + CC * KMO_PLANE);            // [2 KMO_RUN][KMO_RING_INTS] ring of described tiles of this worker
+    l.s_red = (uint32_t*)(l.s_box + 2 * KMO_RUN * KMO_RING_INTS);  // [KMO_NW] (8-byte slots: keeps s_gm aligned); the persistent loop uses two words
     l.s_gm = (double*)(l.s_red + 2 * KMO_NW);               // [KMO_NW][9] matrix-gradient partials of a finished image
     return l;
 }
@@ -1023,11 +829,11 @@ __device__ __forceinline__ void kmo_gm_commit(const double* s_gm, double* gmat_b
 // A tile whose requests have arrived: source tile -> LDS, exact maximum of |grad_out| over its box, coordinate tables
 template <typename T, int CM, int CC>
 __device__ __forceinline__ void kmo_stage(const KmWarpFusedArgs<T>& a, const KmoTile& d, const int* rec, const float (&G)[KMO_SLOTS][CC],
-                                          const float (&S)[CC * KMO_PLANE / KMO_NT], const KmoLds& l, float* s_src_cur, const float (&fillv)[CC], bool is_fill, int lane, int wave, uint32_t par KMO_PROF_PARAMS) {
+                                          const float (&S)[CC * KMO_PLANE / KMO_NT], const KmoLds& l, float* s_src_cur, const float (&fillv)[CC], bool is_fill, int lane, uint32_t par KMO_PROF_PARAMS) {
     // (no early exit for a tile this launch does not own: every path through here must CONSUME the slots and the source registers,
     // or the compiler - which cannot know that nothing was requested for such a tile - waits for them later, inside the scatter, with
     // a wait that also covers the next tile's requests)
-    if constexpr (KMO_SRC_DMA && sizeof(T) == 4) {
+    if constexpr (kmo_dma<T>) {
         // this wave's LDS-DMA requests (issued during the previous item's scatter, in front of most of this item's grad_out requests) have
         // landed: the compiler does not know them - its own waits cover them only when a later load of its own is waited for
         KM_VMCNT0();
@@ -1041,22 +847,11 @@ __device__ __forceinline__ void kmo_stage(const KmWarpFusedArgs<T>& a, const Kmo
     for (int s = 0; s < KMO_SLOTS; ++s)
 #pragma unroll
         for (int c = 0; c < CC; ++c) mb = max(mb, __float_as_uint(G[s][c]) & 0x7fffffffu);
-#if KMO_ABL & 128
-    { int keep = (int)mb; KM_OPAQUE(keep); }  // (the slots are still consumed here: the compiler's waits for them stay where they are)
-    if (lane == 63 && wave == 0) l.s_red[par] = 0x3f800000u;
-#elif KMO_RED_ATOMIC
     // one word per work item (two, alternating): sixteen partials that every wave reads back become one atomic per wave here and one read
     // after the barrier; the wave's maximum through DPP instead of six LDS round trips.  (All 64 lanes ATOMICALLY on the one word: + 12 %
     // on the whole kernel - same-address lanes serialise; profiles/r04/bwd_fused_per_pixel_variants.txt, run 28.)
-    (void)wave;
     mb = km_wave_umax_last(mb);
     if (lane == 63) atomicMax(l.s_red + par, mb);
-#else
-    (void)par;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mb = max(mb, (uint32_t)__shfl_down((int)mb, off, 64));
-    if (lane == 0) l.s_red[wave] = mb;
-#endif
     KMO_T(9)  // stage: maximum of |grad_out|
     if (d.t >= 0 && d.regular && d.nq > 0 && d.p == 0) {
         float m[9];
@@ -1068,7 +863,7 @@ __device__ __forceinline__ void kmo_stage(const KmWarpFusedArgs<T>& a, const Kmo
 
 // ---- launch 2: the persistent loop over the regular tiles -------------------------------------------------------------------------
 template <typename T, int CM, int ALIGN, int CC, int PADX>
-__global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_bwd_fused_kernel(const KmWarpFusedArgs<T> a) {
+__global__ __launch_bounds__(KMO_NT, KMO_NT / 256) void km_warp_bwd_fused_kernel(const KmWarpFusedArgs<T> a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const KmWarpGeom<float>& g = a.g;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1079,19 +874,15 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
 #pragma unroll
     for (int c = 0; c < CC; ++c) fillv[c] = is_fill ? a.fill[c] : 0.f;
     const size_t dst_plane = (size_t)g.h * g.w;
-    constexpr bool DMA = KMO_SRC_DMA && sizeof(T) == 4;  // the source tiles by LDS-DMA, double-buffered (kmo_dma_src)
+    constexpr bool DMA = kmo_dma<T>;
 
     // ---- prologue: records of the first tiles, accumulators zeroed, the first tile requested and staged ----
     if (wave == 0) kmo_fetch_boxes(a, 0u, lane, l.s_box);
     for (int e = tid; e < CC * KMO_PLANE / 4; e += KMO_NT) ((int4*)l.s_acc)[e] = make_int4(0, 0, 0, 0);
-    if (KMO_RED_ATOMIC && tid < 2) l.s_red[tid] = 0u;
+    if (tid < 2) l.s_red[tid] = 0u;  // the two words of the maximum of |grad_out| (kmo_stage)
     __syncthreads();
     KmoTile cur;
-#if KMO_RING_DESC
     kmo_load_desc(kmo_ring(l.s_box, 0u), cur);
-#else
-    kmo_describe(a, kmo_tile_of(a, 0u), kmo_ring(l.s_box, 0u), cur);
-#endif
     float G[KMO_SLOTS][CC];             // grad_out of this thread's pixels: the current tile's, refilled slot by slot with the next tile's
     float S[CC * KMO_PLANE / KMO_NT];   // this thread's part of the source tile on its way to LDS
 #pragma unroll
@@ -1108,7 +899,7 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
             kmo_walk_none(w0);
         }
 #pragma unroll
-        for (int s = 0; s < KMO_SLOTS; ++s) kmo_request_slot<T, CC>(gout_c, dst_plane, g.w, s, w0, G[s]);
+        for (int s = 0; s < KMO_SLOTS; ++s) kmo_request_slot<T, CC>(gout_c, dst_plane, s, w0, G[s]);
     }
     float A[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int pending_b = -1;      // row of gmat whose matrix-gradient partials sit in s_gm
@@ -1126,7 +917,7 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
     unsigned long long tlast = __builtin_amdgcn_s_memtime();
     const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    // A work item is (tile, pass): a box larger than the registers of the workgroup (KMO_CAP pixels: rotations beyond ~10 degrees,
+    // A work item is (tile, pass): a box larger than the registers of the workgroup (KMO_NT * KMO_SLOTS pixels: rotations beyond ~10 degrees,
     // magnification) is walked in several passes, the next pass requested slot by slot during the current one like a next tile.
     for (uint32_t q = 0, item = 0; cur.t >= 0; ++item) {
         // ---- this item's requests have arrived: (first pass: source tile -> LDS, coordinate tables;) exact maximum of |grad_out| over the
@@ -1139,7 +930,7 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
         KMO_T(0)  // wait for this item's requests
         float* const s_src_cur = (DMA && (q & 1u)) ? l.s_src2 : l.s_src;
         float* const s_src_nxt = (DMA && !(q & 1u)) ? l.s_src2 : l.s_src;  // (of tile q + 1)
-        kmo_stage<T, CM, CC>(a, cur, kmo_ring(l.s_box, q), G, S, l, s_src_cur, fillv, is_fill, lane, wave, item & 1u KMO_PROF_ARGS);
+        kmo_stage<T, CM, CC>(a, cur, kmo_ring(l.s_box, q), G, S, l, s_src_cur, fillv, is_fill, lane, item & 1u KMO_PROF_ARGS);
         KMO_T(1)  // stage: source tile -> LDS, maxima, tables
         // ---- flush of the previous tile (zeroes the accumulators) ----
         if (prev.t >= 0) kmo_flush<T, CC>(a, prev, l.s_acc, true, prev_inv_scale, prev_discard);
@@ -1147,18 +938,14 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
         KMO_T(2)  // flush
         const bool last_pass = cur.p + 1 >= cur.npass;
         if (wave == 0 && last_pass && (q + 1u) % KMO_RUN == 0u) kmo_fetch_boxes(a, q + 1u, lane, l.s_box);  // (into the half of the ring tile q is not in)
-        if (!(KMO_ABL & 32)) KM_LDS_BARRIER();  // B1: source tile, maxima, tables in LDS, accumulators zero (first pass)
+        KM_LDS_BARRIER();  // B1: source tile, maxima, tables in LDS, accumulators zero (first pass)
         KMO_T(3)  // barrier B1
 
         // ---- the NEXT item: the next pass of this box, or the first pass of the next tile (whose source tile is requested after the
         //      first slot of the scatter); its grad_out slot by slot during the scatter ----
         KmoTile nxt;
         if (last_pass) {
-#if KMO_RING_DESC
             kmo_load_desc(kmo_ring(l.s_box, q + 1u), nxt);
-#else
-            kmo_describe(a, kmo_tile_of(a, q + 1u), kmo_ring(l.s_box, q + 1u), nxt);
-#endif
         } else {
             nxt = cur;
             nxt.p = cur.p + 1;
@@ -1174,20 +961,14 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
         }
         KMO_T(12)  // description: walk of the next box, plane pointers
         // matrix-gradient partials of the image finished before this tile
-        if (pending_b >= 0) kmo_gm_commit<CM, (KMO_GM_LDS && CC * KMO_PLANE >= 9 * KMO_NT)>(l.s_gm, a.gmat ? a.gmat + (size_t)pending_b * 9 : nullptr, tid);
+        if (pending_b >= 0) kmo_gm_commit<CM, kmo_gm_lds<CC>>(l.s_gm, a.gmat ? a.gmat + (size_t)pending_b * 9 : nullptr, tid);
         pending_b = -1;
         KMO_T(13)  // description: matrix-gradient commit
 
         // ---- the fixed-point scale: from the exact maximum of the first pass; a later pass with a larger one rescales the accumulators ----
         if (cur.p == 0) tile_ok = cur.regular;
         if (cur.regular && tile_ok) {
-#if KMO_RED_ATOMIC
             uint32_t Mb = l.s_red[item & 1u];
-#else
-            uint32_t Mb = l.s_red[0];
-#pragma unroll
-            for (int w = 1; w < KMO_NW; ++w) Mb = max(Mb, l.s_red[w]);
-#endif
             Mb = (uint32_t)kmt_uniform((int)Mb);
             if (Mb >= 0x7f800000u) {
                 // NaN / inf in the box: IEEE float accumulation is the general launch's; mark the tile and leave it alone (what earlier
@@ -1220,27 +1001,23 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
         {
             float m[9];
             kmo_matrix(kmo_ring(l.s_box, q), m);
-            kmo_process<T, CM, ALIGN, CC, true, true, PADX>(m, cur, kc, G, l.s_u4, l.s_v4, l.s_acc, s_src_cur, scale, A, g.w, wn, gout_n, dst_plane, mine, a, nxt, S, s_src_nxt);
+            kmo_process<T, CM, ALIGN, CC, true, true, PADX>(m, cur, kc, G, l.s_u4, l.s_v4, l.s_acc, s_src_cur, scale, A, wn, gout_n, dst_plane, mine, a, nxt, S, s_src_nxt);
         }
         KMO_T(5)  // scatter
-        if (!(KMO_ABL & 64)) KM_LDS_BARRIER();  // B2: every contribution of the pass is in the accumulators; the tables, s_red and (last pass) the source tile are free
+        KM_LDS_BARRIER();  // B2: every contribution of the pass is in the accumulators; the tables, s_red and (last pass) the source tile are free
         KMO_T(6)  // barrier B2
         // (this item's maximum has been read by every wave; the word's next writers - the item after the next - are behind the next B1)
-        if (KMO_RED_ATOMIC && tid == 0) l.s_red[item & 1u] = 0u;
+        if (tid == 0) l.s_red[item & 1u] = 0u;
 
         if (last_pass) {
             // ---- an image that ends here publishes its matrix-gradient partials ----
-            if ((KMO_ABL & 16) && (nxt.t < 0 || nxt.b != cur.b)) {  // (ablation: the partials are consumed - their arithmetic stays - and dropped)
-#pragma unroll
-                for (int k = 0; k < 9; ++k) { KM_OPAQUE(A[k]); A[k] = 0.f; }
-            }
-            if (!(KMO_ABL & 16) && (nxt.t < 0 || nxt.b != cur.b)) {  // (per (image, group): the groups of an image meet in gmat's atomics)
-                if (KMO_GM_LDS && CC * KMO_PLANE >= 9 * KMO_NT) {
+            if (nxt.t < 0 || nxt.b != cur.b) {  // (per (image, group): the groups of an image meet in gmat's atomics)
+                if (kmo_gm_lds<CC>) {
                     // Nine 64-lane fp64 reductions per wave are 108 ds_bpermute + 54 v_add_f64 for each of the 16 waves - 2 000 cycles per tile on
                     // average (profiles/r03_bwd_phases.txt: "loop tail").  The source tile is dead after the last pass of its tile: the 1024
                     // threads park their nine fp32 partials there, and wave k sums row k - sixteen conflict-free reads per lane, fp64 adds, ONE
                     // wave reduction.  The same fp32 partials summed in fp64, in another order; two more LDS barriers per image.
-                    float* s_part = s_src_cur;  // (KMO_SRC_DMA: the other buffer is receiving the next tile)
+                    float* s_part = s_src_cur;  // (fp32 storage: the other buffer is receiving the next tile)
 #pragma unroll
                     for (int k = 0; k < 9; ++k) { s_part[k * KMO_NT + tid] = A[k]; A[k] = 0.f; }
                     KM_LDS_BARRIER();
@@ -1287,7 +1064,7 @@ __global__ __launch_bounds__(KMO_NT, KMO_WG_PER_CU * KMO_NT / 256) void km_warp_
 #endif
     // ---- epilogue: the last image's partials ----
     __syncthreads();
-    if (pending_b >= 0) kmo_gm_commit<CM, (KMO_GM_LDS && CC * KMO_PLANE >= 9 * KMO_NT)>(l.s_gm, a.gmat ? a.gmat + (size_t)pending_b * 9 : nullptr, tid);
+    if (pending_b >= 0) kmo_gm_commit<CM, kmo_gm_lds<CC>>(l.s_gm, a.gmat ? a.gmat + (size_t)pending_b * 9 : nullptr, tid);
 }
 
 // ---- launch 3, first part: non-finite gradients at output pixels NO tile visits ---------------------------------------------------
@@ -1346,15 +1123,8 @@ __device__ __forceinline__ bool kmo_scan_maybe_unvisited(float x, float y, float
     return !((x > -1.f + e) && (x < W - e) && (y > -1.f + e) && (y < H - e));
 }
 #define KMO_SCAN_BLK 16
-#ifndef KMO_SCAN_FORK
-#define KMO_SCAN_FORK 1   // 0: the scan's launch stays on the launch stream, between the boxes and the persistent loop (A/B)
-#endif
-#ifndef KMO_SCAN_NB
 #define KMO_SCAN_NB 2   // candidate blocks a wave scans at a time
-#endif
-#ifndef KMO_SCAN_CH
 #define KMO_SCAN_CH 3   // channels whose loads fly together
-#endif
 // One workgroup classifies KMO_NT blocks at a time (thread = block: its four corners), compacts the candidates into an LDS list and deals
 // them to its 16 waves - the candidates are the blocks along the image's borders, i.e. whole rows of blocks: left with the wave that
 // classified them, a few waves walked 30 - 60 blocks each while the rest had none (180 us for the launch; profiles/r04/bwd_general_launch_grid.txt).
@@ -1612,7 +1382,7 @@ static int kmo_launch_k(const KmWarpFusedArgs<T>& a, hipStream_t s) {
         const uint64_t want = (nblk + KMO_SCAN_NT - 1) / KMO_SCAN_NT;
         const int cus = km_device_cus();
         const uint64_t cap = (uint64_t)(cus > 0 ? cus : 2) * 4u;  // (one wave per SIMD beside the persistent workgroup: 4 waves = 1 workgroup per CU at a time; a few rounds)
-        hipStream_t side = KMO_SCAN_FORK ? km_side_fork(s) : nullptr;
+        hipStream_t side = km_side_fork(s);
         hipLaunchKernelGGL((km_warp_bwd_scan_kernel<T, CM, ALIGN>), dim3((unsigned)(want < cap ? (want ? want : 1) : cap)), dim3(KMO_SCAN_NT), 0, side ? side : s, a);
         forked = side != nullptr;
     }
@@ -1621,17 +1391,9 @@ static int kmo_launch_k(const KmWarpFusedArgs<T>& a, hipStream_t s) {
         const int rc = km_side_join(s);
         if (rc != 0) return rc;
     }
-#ifndef KMO_NO_GENERAL  // (variant libraries only: what the launch itself costs)
-    {
-        const uint32_t ngroups = (a.ntiles + a.general_tiles - 1u) / a.general_tiles;
-#ifdef KMO_GENERAL_FULL_GRID
-        const uint32_t ggrid = ngroups;
-#else
-        const uint32_t ggrid = ngroups < a.general_grid ? ngroups : a.general_grid;
-#endif
-        hipLaunchKernelGGL((km_warp_bwd_general_kernel<T, CM, ALIGN, CC, PADX>), dim3(ggrid), dim3(KMO_NT), (size_t)lds, s, a);
-    }
-#endif
+    const uint32_t ngroups = (a.ntiles + a.general_tiles - 1u) / a.general_tiles;
+    const uint32_t ggrid = ngroups < a.general_grid ? ngroups : a.general_grid;
+    hipLaunchKernelGGL((km_warp_bwd_general_kernel<T, CM, ALIGN, CC, PADX>), dim3(ggrid), dim3(KMO_NT), (size_t)lds, s, a);
     return km_check_launch("km_warp2d_bwd(fused)");
 }
 template <typename T, int CM, int PADX>
@@ -1656,11 +1418,7 @@ static int kmo_run_groups(KmWarpFusedArgs<T>& a, int B, uint32_t c0, uint32_t ng
     const uint64_t ntiles = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B * ngrp;
     a.ntiles = (uint32_t)ntiles;
     const int cus = km_device_cus();
-#ifdef KMO_WORKERS_OVERRIDE  // (variant libraries only: fewer persistent workgroups than CUs - what the clock does when part of the chip idles)
-    const uint32_t workers_max = KMO_WORKERS_OVERRIDE;
-#else
-    const uint32_t workers_max = cus > 0 ? (uint32_t)cus * KMO_WG_PER_CU : 3u;  // (the host build of the kernels reports 0 CUs: a few workers, several tiles each)
-#endif
+    const uint32_t workers_max = cus > 0 ? (uint32_t)cus : 3u;  // (the host build of the kernels reports 0 CUs: a few workers, several tiles each)
     // a run = a row of tiles of one image when that still gives every CU several runs; single tiles otherwise
     const uint64_t rows = (uint64_t)a.tiles_y * (uint64_t)B * ngrp;
     a.run_len = (rows >= 4ull * workers_max) ? a.tiles_x : 1u;

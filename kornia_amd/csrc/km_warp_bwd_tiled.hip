@@ -35,13 +35,9 @@
 
 #include "km_warp_tile.h"
 
-#ifndef KMT_NT
 #define KMT_NT 512          // threads per workgroup
-#endif
 #define KMT_NW (KMT_NT / 64)
-#ifndef KMT_UNROLL
 #define KMT_UNROLL 2       // pixels in flight per thread in the scatter loop
-#endif
 #define KMT_CC 3            // channels per pass
 #define KMT_LDS_BYTES ((KMT_BAND_W + KMT_TAB) * 16 + KMT_CC * KMT_PLANE * 4)
 
@@ -390,9 +386,7 @@ __device__ __forceinline__ void kmt_tile_chunk(const KmWarpTiledArgs<T>& a, cons
 }
 
 // Tile-owner SCATTER with fixed-point LDS accumulators (see the file header and kmt_tile_chunk).
-#ifndef KMT_MIN_WAVES
-#define KMT_MIN_WAVES 6
-#endif
+#define KMT_MIN_WAVES 6     // minimum waves per SIMD asked of the register allocation (__launch_bounds__)
 
 // one tile (tx, ty) of image b, all channels: the body of a workgroup
 template <typename T, int CM, int ALIGN>

@@ -19,16 +19,11 @@
 //     bit-identical to km_warp_fwd_kernel<INTERP = bicubic> (tests compare the two);
 //   * a wave whose footprints are not all inside the staged box (box larger than the LDS tile under minification, NaN
 //     positions, vanishing line) gathers its taps from global memory with the generic kernel's per-tap bounds test.
-#ifndef KMQ_FILL_DMA
-#define KMQ_FILL_DMA 1   // fp32 storage: the source box by LDS-DMA (kmf_stage_box_dma)
-#endif
-#ifndef KMQ_TW
-#define KMQ_TW 64
+#define KMQ_TW 64     // output tile of a workgroup
 #define KMQ_TH 32
-#define KMQ_PITCH 80
-#define KMQ_ROWS 80
-#endif
-// TOLERANCE SPENT (round 6, KMQ_FMA = 1).  BASELINE.json asks for 1e-5 against the reference; rounds 2-5 kept this kernel's arithmetic operation for
+#define KMQ_PITCH 80  // floats per staged source row
+#define KMQ_ROWS 80   // staged source rows
+// TOLERANCE SPENT (round 6; in the history as the switch KMQ_FMA).  BASELINE.json asks for 1e-5 against the reference; rounds 2-5 kept this kernel's arithmetic operation for
 // operation that of the generic kernel (35 vector instructions per channel for the 4 x 4 taps - 20 multiplies, 15 adds, every product rounded
 // - and 25 per axis for the coefficients), bit-identical to it, <= 1e-6 from the reference (whose own vectorised CPU kernel sums in another
 // order) - and sat on its issue time: ~125 vector instructions per grey pixel, 0.37 ms = 0.36 of the HBM roofline at config 4.  With fused
@@ -36,19 +31,11 @@
 // (15 per axis): the same association, products no longer rounded before they are added - each result at least as close to the exact value
 // as the reference's, <= 2e-6 from the oracle and <= 1e-5 from the live reference (asserted: tests/test_gpu_config_parity.py,
 // tests/test_gpu_warp.py, tests/test_oracle_live_sweep.py).  Both paths of this kernel (LDS taps, gather rows) use the same form, so a result
-// still never depends on the box estimate.  KMQ_FMA = 0 restores the exact form (A/B).
-#ifndef KMQ_FMA
-#define KMQ_FMA 1
-#endif
+// still never depends on the box estimate.
 __device__ __forceinline__ float kmq_dot4(float t0, float t1, float t2, float t3, const float (&c)[4]) {
-#if KMQ_FMA
     return km_fma(t3, c[3], km_fma(t2, c[2], km_fma(t1, c[1], t0 * c[0])));
-#else
-    return t0 * c[0] + t1 * c[1] + t2 * c[2] + t3 * c[3];
-#endif
 }
 __device__ __forceinline__ void kmq_coeffs(float t, float (&c)[4]) {
-#if KMQ_FMA
     const float A = -0.75f;
     float x = t + 1.0f;
     c[0] = km_fma(km_fma(km_fma(A, x, -5 * A), x, 8 * A), x, -4 * A);
@@ -58,15 +45,7 @@ __device__ __forceinline__ void kmq_coeffs(float t, float (&c)[4]) {
     c[2] = km_fma(km_fma(A + 2, x, -(A + 3)) * x, x, 1.0f);
     x = x + 1.0f;
     c[3] = km_fma(km_fma(km_fma(A, x, -5 * A), x, 8 * A), x, -4 * A);
-#else
-    km_cubic_coeffs(t, c);
-#endif
 }
-#ifndef KMQ_ST16
-#define KMQ_ST16 0   // 1: fp32 storage, the thread's results leave as 16-byte stores after a 4 x 4 transpose inside each quad of lanes (km_quad_transpose4).
-                     // MEASURED SLOWER (round 6, profiles/r06/run2_*, same box, same bits): config 4 361.6 / 359.8 us against 333.7 / 331.2 with one dword
-                     // per lane and row (and 397.8 against 365.2 on the exact-rounding form): like the box forward, DESIGN.md 4.6
-#endif
 
 template <typename T, int CM, int NC, int ALIGN>
 __device__ __forceinline__ void kmq_rows_gather(const KmWarpArgs<T>& a, const float (&m)[9], const float4* s_rv, const KmlHalf& cu, bool fast, uint32_t b,
@@ -153,13 +132,11 @@ __global__ __launch_bounds__(256) void km_warp_fwd_cubic_kernel(const KmWarpArgs
         float oob[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) oob[c] = 0.f;
-#if KMQ_FILL_DMA
         if constexpr (sizeof(T) == 4) {
             // fp32 storage: the whole box by LDS-DMA, every pass in flight together (the register copy is three round trips for an 80-row box)
             kmf_stage_box_dma<NC, PITCH, ROWS>(reinterpret_cast<const float*>(src_b), src_plane, W, H, bx, s_src);
             KM_VMCNT0();
         } else
-#endif
             kmf_stage_box_dyn<T, NC, PITCH>(src_b, src_plane, W, H, bx, s_src, oob);
         __syncthreads();
     }
@@ -210,31 +187,7 @@ __global__ __launch_bounds__(256) void km_warp_fwd_cubic_kernel(const KmWarpArgs
             }
         }
         if (__all(all_in)) {  // wave-uniform: every footprint of the wave was in the box - the results are final
-#if KMQ_ST16
-            if constexpr (sizeof(T) == 4 && RPT % 4 == 0) {
-                // 16-byte stores: the quad's 4 columns x 4 of the thread's rows (RSTEP apart) transposed in registers, lane q of the quad writes
-                // the four pixels of row r0 + q.  (Output rows are 16-byte aligned runs of whole quads: lanes right of the image left above.)
-                if (((g.w & 3) == 0) && (((uintptr_t)a.dst & 15) == 0)) {
-                    const int q4 = tid & 3;
-#pragma unroll
-                    for (int r0 = 0; r0 < RPT; r0 += 4) {
-                        if ((int)ty * TH + r0 * RSTEP >= g.h) break;  // block-uniform
-                        const int i = i_base + (r0 + q4) * RSTEP;
-#pragma unroll
-                        for (int c = 0; c < NC; ++c) {
-                            float v4[4] = {res[c][r0], res[c][r0 + 1], res[c][r0 + 2], res[c][r0 + 3]};
-                            km_quad_transpose4(v4, q4);
-                            if (i < g.h) {
-                                float* p = reinterpret_cast<float*>(dst_b) + (size_t)c * dst_plane + (size_t)i * g.w + (size_t)(j & ~3);
-                                KM_CHECK_ALIGNED(p, 16);
-                                km_st4_c<true>(p, v4);
-                            }
-                        }
-                    }
-                    return;
-                }
-            }
-#endif
+            // (one dword per lane and row: 16-byte stores after a quad transpose measured 8 % slower here too, profiles/r06/run2_*)
 #pragma unroll
             for (int r = 0; r < RPT; ++r) {
                 const int i = i_base + r * RSTEP;

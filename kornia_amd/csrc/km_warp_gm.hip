@@ -19,7 +19,7 @@
 #include "km_warp_gm_rows.h"
 
 template <typename T, int CM, int NC, int ALIGN>  // NC = 3 / 1: RGB / grey unrolled ; NC = 0: runtime channel loop
-__global__ KMG_BOUNDS void km_warp_gm_kernel(const KmWarpGmArgs<T> a) {
+__global__ __launch_bounds__(256) void km_warp_gm_kernel(const KmWarpGmArgs<T> a) {
     const KmWarpGeom<float>& g = a.g;
     __shared__ double red[4][9];
     __shared__ float4 s_rv[KMG_TILE_H];  // per row of the tile: (m1 v, m4 v, m7 v, v)

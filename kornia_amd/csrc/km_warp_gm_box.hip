@@ -20,22 +20,13 @@
 
 #include "km_warp_gm_rows.h"
 
-#ifndef KMGB_PITCH
-#define KMGB_PITCH 80
-#define KMGB_ROWS 40
-#endif
-#define KMGB_TW 64
+#define KMGB_PITCH 80  // floats per staged source row of the box
+#define KMGB_ROWS 40   // staged source rows
+#define KMGB_TW 64  // output region of a workgroup
 #define KMGB_TH 32
-#ifndef KMGB_WAVES_PER_EU
-#define KMGB_WAVES_PER_EU 4
-#endif
+#define KMGB_WAVES_PER_EU 4  // minimum waves per SIMD (__launch_bounds__): four workgroups per CU
 #define KMGB_RPT (KMGB_TH / (256 / KMGB_TW))  // output rows per thread (consecutive)
-#ifndef KMGB_ILP
-#define KMGB_ILP 2
-#endif
-#ifndef KMGB_ABL
-#define KMGB_ABL 0  // timing experiments only (wrong results): 1 no block reduction / atomics, 2 no sampling pass, 4 no grad_out loads
-#endif
+#define KMGB_ILP 2  // rows of a thread sampled together on the fast path
 
 // the region once its box is known to fit: requests, positions (in-box vote), barrier, sampling.  Returns false - block-uniform, nothing added to
 // the sums - when a footprint of the region lies outside the box.  FAST: the division operands of every row are in the shared-reciprocal range.
@@ -64,7 +55,7 @@ __device__ __forceinline__ bool kmgb_staged(const KmWarpGmArgs<float>& a, const 
             ok[r] = col_ok & (i < g.h);
             const uint32_t off = ok[r] ? (uint32_t)i * (uint32_t)g.w + (uint32_t)j : 0u;
 #pragma unroll
-            for (int c = 0; c < NC; ++c) go[r][c] = (KMGB_ABL & 4) ? (float)(off & 7u) : km_ld(km_at(gout_b + c * dst_plane, off));
+            for (int c = 0; c < NC; ++c) go[r][c] = km_ld(km_at(gout_b + c * dst_plane, off));
         }
         // ---- positions, while the requests fly: only to know that every footprint lies in the box.  They are formed AGAIN at the sampling
         //      (the same instructions on the same operands: the same bits) - eight rows' worth of position records, held across the barrier
@@ -86,10 +77,6 @@ __device__ __forceinline__ bool kmgb_staged(const KmWarpGmArgs<float>& a, const 
         KM_VMCNT0();  // (this wave's LDS-DMA requests have landed - and its grad_out loads with them)
         if (__syncthreads_and((int)inbox)) {  // block-uniform (the reduction below has a barrier)
             done = true;
-#if KMGB_ABL & 2
-            S[0] = go[0][0] + go[RPT - 1][NC - 1] + s_src[threadIdx.x];
-            return done;
-#endif
             KmlHalf cu2 = cu;
             KM_OPAQUE(cu2.a); KM_OPAQUE(cu2.b); KM_OPAQUE(cu2.c);  // (a new value to the optimiser: nothing of the first pass is kept alive for this one)
 #pragma unroll
@@ -164,16 +151,7 @@ __global__ __launch_bounds__(256, KMGB_WAVES_PER_EU) void km_warp_gm_box_kernel(
         if (bx.fast) km_warp_gm_rows<float, CM, NC, ALIGN, true, RPT, 1>(a, m, s_rv, b, j, li_base, i_base, S, Sv);
         else km_warp_gm_rows<float, CM, NC, ALIGN, false, RPT, 1>(a, m, s_rv, b, j, li_base, i_base, S, Sv);
     }
-#if KMGB_ABL & 1
-    {
-        float keep = ((S[0] + S[1]) + S[2]) + ((Sv[0] + Sv[1]) + Sv[2]);
-        KM_OPAQUE(keep);
-        if (keep == 12345.678f) gmat_b[0] = (double)u;
-        (void)red;
-    }
-#else
     kmg_block_reduce<CM>(S, Sv, u, gmat_b, red);
-#endif
 }
 
 template <int CM, int NC>

@@ -4,20 +4,11 @@
 
 #include "km_warp_stage.h"
 
-#ifndef KMG_ROWS
-#define KMG_ROWS 16
-#endif
+#define KMG_ROWS 16  // output rows per thread
 #define KMG_TILE_W 64
-#ifndef KMG_GROUP
 #define KMG_GROUP 2   // rows whose loads are in flight together
-#endif
-#ifndef KMG_PATCH_W
 #define KMG_PATCH_W 32  // measured at 256x3x512^2: 64 -> 0.375 ms (0.83 at 20 deg, 1.32 at 45 deg), 32 -> 0.368 (0.60, 0.84), 16 -> 0.412 (0.57, 0.68)
-#endif
 #define KMG_TILE_H (4 * KMG_ROWS)
-#ifndef KMG_BOUNDS
-#define KMG_BOUNDS __launch_bounds__(256)
-#endif
 
 template <typename T>
 struct KmWarpGmArgs {

@@ -13,15 +13,9 @@
 #include "km_lean.h"
 #include "km_regtile.h"
 
-#ifndef KMF_T
 #define KMF_T 32        // output tile (square: the source box stays small under rotation)
-#endif
-#ifndef KMF_PITCH
 #define KMF_PITCH 56    // floats per staged source row (box width + alignment slack), multiple of 4
-#endif
-#ifndef KMF_ROWS
 #define KMF_ROWS 56     // staged source rows
-#endif
 #define KMF_RPT (KMF_T * KMF_T / 256)   // output rows per thread
 #define KMF_RSTEP (256 / KMF_T)          // tile rows between a thread's consecutive rows
 

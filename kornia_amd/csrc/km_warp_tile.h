@@ -5,12 +5,8 @@
 
 #include "km_lean.h"
 
-#ifndef KMT_TW
 #define KMT_TW 64           // tile width  (the flush maps lane -> column: keep 64)
-#endif
-#ifndef KMT_TH
 #define KMT_TH 64           // tile height
-#endif
 #define KMT_BAND_W 128      // output columns per band = capacity of the column table (float4 entries)
 #define KMT_TAB 128         // output rows per band = capacity of the row table (float4 entries)
 #define KMT_PLANE (KMT_TH * KMT_TW)
@@ -38,10 +34,6 @@ struct KmtBox {
     bool fixed_ok;  // bounded multiplicity: fixed-point accumulation is accurate enough
     bool ok;        // the box is the tile's own (false: the whole output - vanishing line, degenerate map)
 };
-
-#ifndef KMT_TIGHT_BOX
-#define KMT_TIGHT_BOX 1
-#endif
 
 // G = (output index <- source pixel) as a projective map: (Jn, In, D) = G (x, y, 1), (j, i) = (Jn, In) / D.
 // A projective map sends the tile rectangle (grown by the 1-pixel footprint) to a convex quad when D keeps
@@ -114,14 +106,12 @@ __device__ __forceinline__ KmtBox kmt_tile_box(const KmWarpGeom<float>& g, const
             imin = fminf(imin, fi); imax = fmaxf(imax, fi);
             njx = fmaxf(njx, fabsf(G[0] * D - Jn * G[6])); njy = fmaxf(njy, fabsf(G[1] * D - Jn * G[7]));
             nix = fmaxf(nix, fabsf(G[3] * D - In * G[6])); niy = fmaxf(niy, fabsf(G[4] * D - In * G[7]));
-            if (KMT_TIGHT_BOX) {
-                const R axs = fabsf(xs[cx]), ays = fabsf(ys[cy]);
-                const R Ja = Ga[0] * axs + Ga[1] * ays + Ga[2], Ia = Ga[3] * axs + Ga[4] * ays + Ga[5], Da = Ga[6] * axs + Ga[7] * ays + Ga[8];
-                const R invd = 1.0f / fabsf(D);
-                egj = fmaxf(egj, (Ja + fabsf(fj) * Da) * invd);
-                egi = fmaxf(egi, (Ia + fabsf(fi) * Da) * invd);
-                drel = fmaxf(drel, Da * invd);
-            }
+            const R axs = fabsf(xs[cx]), ays = fabsf(ys[cy]);
+            const R Ja = Ga[0] * axs + Ga[1] * ays + Ga[2], Ia = Ga[3] * axs + Ga[4] * ays + Ga[5], Da = Ga[6] * axs + Ga[7] * ays + Ga[8];
+            const R invd = 1.0f / fabsf(D);
+            egj = fmaxf(egj, (Ja + fabsf(fj) * Da) * invd);
+            egi = fmaxf(egi, (Ia + fabsf(fi) * Da) * invd);
+            drel = fmaxf(drel, Da * invd);
         }
     const bool same_sign = (dmin > 0.f) || (dmax < 0.f);
     const R dabs_min = fminf(fabsf(dmin), fabsf(dmax)), dabs_max = fmaxf(fabsf(dmin), fabsf(dmax));
@@ -137,7 +127,7 @@ __device__ __forceinline__ KmtBox kmt_tile_box(const KmWarpGeom<float>& g, const
     const R jac_j = (njx + njy) * inv_d2, jac_i = (nix + niy) * inv_d2;  // |dj/dx| + |dj/dy|, |di/dx| + |di/dy| over the tile
     R mj = 1.0f, mi = 1.0f;     // margins in output pixels; with floor / ceil below this is the first version's box
     bool flat_box = true;
-    if (KMT_TIGHT_BOX) {
+    {  // the tight margins, where their first-order bounds can be trusted
         const R gamma = 64.0f * 5.9604645e-8f;  // ~10 roundings per quantity, x6 safety
         // forward rounding: the position of output pixel (j, i) is N / Dn with |u|, |v| <= U, V; Dn is affine in
         // (u, v), so its smallest magnitude over the (flat-margin) box is attained at a corner

@@ -11,8 +11,10 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "kornia_amd", "csrc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt",
-         "--cuda-device-only", "-S"]
+sys.path.insert(0, ROOT)
+from kornia_amd.build import FILE_FLAGS, HIPCC_FLAGS  # noqa: E402  (the flags the library ships with, per file)
+
+FLAGS = [*HIPCC_FLAGS, "--cuda-device-only", "-S"]
 
 
 def kernels(asm_path):
@@ -46,7 +48,7 @@ def main():
                 print(f"{f}: new file")
                 continue
             a, b = os.path.join(tmp, f + ".a.s"), os.path.join(tmp, f + ".b.s")
-            procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", *FLAGS, src, "-o", dst], stderr=subprocess.DEVNULL)
+            procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", *FLAGS, *FILE_FLAGS.get(f, []), src, "-o", dst], stderr=subprocess.DEVNULL)
                      for src, dst in ((old_src, a), (os.path.join(CSRC, f), b))]
             if any(p.wait() for p in procs):
                 print(f"{f}: compile failed")

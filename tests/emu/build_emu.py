@@ -15,8 +15,8 @@ EMU = os.path.join(ROOT, "tests", "emu")
 ASAN = os.environ.get("KM_EMU_ASAN", "") not in ("", "0")
 # KM_EMU_UBSAN=1: UndefinedBehaviorSanitizer build (signed overflow in index arithmetic, misaligned typed accesses, bad shifts ...)
 UBSAN = os.environ.get("KM_EMU_UBSAN", "") not in ("", "0")
-# KM_EMU_DEFS="-DKMB_UPDOWN=1 ...": extra preprocessor definitions (variant builds of the kernels, as profiles/build_variant2.sh makes for the
-# device), in a build directory of their own
+# KM_EMU_DEFS="-DKMO_DEV_F32_ONLY ...": extra preprocessor definitions, in a build directory of their own (the A/B switches of the warp kernels
+# that profiles/build_variant2.sh built for the device were removed, see commit a903246)
 DEFS = os.environ.get("KM_EMU_DEFS", "").split()
 _TAG = ("_asan" if ASAN else ("_ubsan" if UBSAN else "")) + ("_" + "".join(c if c.isalnum() else "_" for c in "".join(DEFS)) if DEFS else "")
 OUT = os.path.join(ROOT, "tests", "_build", "emu" + _TAG)

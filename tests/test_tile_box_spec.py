@@ -64,7 +64,7 @@ def _build(name, mutate=None):
     box = _span(os.path.join(CSRC, "km_warp_tile.h"), "tile_box")
     if mutate is not None:
         box = mutate(box)
-    code = SHIM + _span(os.path.join(CSRC, "km_sampler.h"), "coords") + "\n#define KMT_TIGHT_BOX 1\n" + box + WRAP
+    code = SHIM + _span(os.path.join(CSRC, "km_sampler.h"), "coords") + "\n" + box + WRAP
     open(src, "w").write(code)
     subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", src, "-o", so], check=True)
     lib = ctypes.CDLL(so)
