@@ -138,9 +138,10 @@ __device__ __forceinline__ R km_unnormalize(R g, int size, int align, R& mult) {
     return km_fma(g + 1, (R)size / 2, (R)-0.5);  // ((g+1)*size - 1)/2 as one fused op (see oracle)
 }
 
+// (a NaN position clips to 0 with a zero derivative, like -inf: ATen's CPU sampler clamps with max(x, 0) in the operand order that drops a NaN)
 template <typename R>
 __device__ __forceinline__ R km_clip(R x, int size, R& grad) {
-    if (x <= (R)0) {
+    if (!(x > (R)0)) {
         grad = 0;
         return 0;
     }
@@ -170,8 +171,11 @@ __device__ __forceinline__ R km_reflect(R x, int twice_low, int twice_high, R& g
         sign = 1;
     }
     const R extra = km_fmod(x, span);
-    const int flips = (int)km_floor(x / span);
-    if (flips % 2 == 0) {
+    // parity of the fold count in floating point: the count itself passes INT_MAX for a far-away position (an undefined float -> int conversion).
+    // A NaN / inf position has a NaN remainder and comes out NaN, which the clip that follows every reflection brings to 0
+    const R flips = km_floor(x / span);
+    const bool even = km_floor(flips * (R)0.5) * (R)2 == flips;  // (exact: halving and doubling round nothing)
+    if (even) {
         grad = (R)sign;
         return extra + mn;
     }

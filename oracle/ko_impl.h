@@ -180,8 +180,9 @@ static inline REAL KO(ko_unnormalize)(REAL g, int size, int align, REAL* mult) {
     return KO(ko_fma)(g + 1, (REAL)size / 2, (REAL)-0.5);
 }
 
+/* a NaN position clips to 0 like -inf (ATen's CPU sampler: max(x, 0) in the operand order that drops a NaN) */
 static inline REAL KO(ko_clip)(REAL x, int size, REAL* grad) {
-    if (x <= (REAL)0) { *grad = 0; return 0; }
+    if (!(x > (REAL)0)) { *grad = 0; return 0; }
     REAL mx = (REAL)(size - 1);
     if (x >= mx) { *grad = 0; return mx; }
     *grad = 1;
@@ -196,8 +197,10 @@ static inline REAL KO(ko_reflect)(REAL x, int twice_low, int twice_high, REAL* g
     x = x - mn;
     if (x < (REAL)0) { sign = -1; x = -x; } else { sign = 1; }
     REAL extra = KO_FMOD(x, span);
-    int flips = (int)KO_FLOOR(x / span);
-    if (flips % 2 == 0) { *grad = (REAL)sign; return extra + mn; }
+    /* parity of the fold count in floating point (the count passes INT_MAX far away); NaN / inf come out NaN and the clip that follows gives 0 */
+    REAL flips = KO_FLOOR(x / span);
+    int even = KO_FLOOR(flips * (REAL)0.5) * (REAL)2 == flips;
+    if (even) { *grad = (REAL)sign; return extra + mn; }
     *grad = (REAL)(-sign);
     return span - extra + mn;
 }
