@@ -33,7 +33,8 @@
  *     bit 0  km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd (masks, RandomPerspective and inverse() of the
  *            augmentation container);
  *     bit 1  km_crop_resize_fwd (crop_by_indices, RandomResizedCrop and the random flips);
- *     bit 2  km_median_blur_supported, km_median_blur_fwd, km_median_blur_bwd (median_blur, MedianBlur, RandomMedianBlur).
+ *     bit 2  km_median_blur_supported, km_median_blur_fwd, km_median_blur_bwd (median_blur, MedianBlur, RandomMedianBlur);
+ *     bit 3  km_bilateral_blur_fwd, km_bilateral_blur_bwd (bilateral_blur, joint_bilateral_blur, BilateralBlur, JointBilateralBlur).
  */
 #ifndef KORNIA_AMD_H
 #define KORNIA_AMD_H
@@ -50,6 +51,8 @@ enum { KM_NEAREST = 0, KM_BILINEAR = 1, KM_BICUBIC = 2 };
 enum { KM_ZEROS = 0, KM_BORDER = 1, KM_REFLECTION = 2, KM_FILL = 3 };
 /* filter border modes (F.pad modes) */
 enum { KM_CONSTANT = 0, KM_REFLECT = 1, KM_REPLICATE = 2, KM_CIRCULAR = 3 };
+/* colour distance of the bilateral filters */
+enum { KM_DIST_L1 = 0, KM_DIST_L2 = 1 };
 
 int km_abi_version(void);
 /* bit mask of the entry-point groups added after set 3 (see Versioning) */
@@ -389,6 +392,33 @@ int km_median_blur_fwd(const void* x, void* y, void* idx, const void* apply, int
                        void* stream);
 int km_median_blur_bwd(const void* gy, const void* idx, const void* apply, void* gx, int B, int C, int H, int W, int ky, int kx, int dtype,
                        void* stream);
+
+/* ---- bilateral_blur / joint_bilateral_blur (km_abi_features() bit 3) -----------------------------
+ * Replaces kornia/filters/bilateral.py:32-84 (F.pad + two unfolds into (B, C, H, W, ky kx) copies + about ten elementwise passes + two
+ * reductions, and autograd through all of it).  One pass each way.  For sample b and output pixel q, with i over the window and q + i through the
+ * border rule of F.pad (KM_CONSTANT: zeros, which take part in D and in the sums):
+ *     D_qi = (sum_c |g^c(q+i) - g^c(q)|)^2 (KM_DIST_L1)  or  sum_c (g^c(q+i) - g^c(q))^2 (KM_DIST_L2)
+ *     k_qi = space_b[i] exp(coef_b D_qi)        W_q = sum_i k_qi        y^c_q = (sum_i k_qi x^c(q+i)) / W_q
+ * No tap is skipped and nothing is clamped (0 * inf and inf - inf are NaN as in the reference).  f32 / bf16 / f16 compute in fp32 (exp as
+ * exp2 with log2(e) folded into coef), f64 in fp64.
+ *   x       (B,C,H,W) dtype
+ *   guide   (B,Cg,H,W) dtype, nullable: null = self-guided (bilateral_blur: g = x, Cg is ignored)
+ *   space   (Bs, ky kx) compute type (fp32; fp64 for f64), Bs = 1 or B: the spatial kernel, row-major
+ *   coef    (Bc) compute type, Bc = 1 or B: -0.5 / sigma_color^2
+ *   y       (B,C,H,W) dtype
+ *   wsum    (B,H,W) compute type, nullable: W_q, written only when given (the backward reads it)
+ * km_bilateral_blur_bwd: from the forward's x, guide, space, coef, y, wsum and gy (B,C,H,W) dtype, a gather without atomics (the same bits
+ * from run to run), each output written once:
+ *   gx      (B,C,H,W) dtype: self-guided - required, the value gradient plus the gradient through the weights; joint - nullable, the value gradient
+ *   gguide  (B,Cg,H,W) dtype, nullable, joint only: the gradient through the weights (l1: a tap whose guidance equals the centre's in a
+ *           channel contributes 0 in that channel, sign(0) = 0)
+ * Limits (< 0 with a km_last_error() message otherwise): ky, kx odd, 1 .. 15; C and Cg at most 16; Bs, Bc in {1, B}; KM_REFLECT needs
+ * ky / 2 < H and kx / 2 < W, KM_CIRCULAR ky / 2 <= H and kx / 2 <= W; H W < 2^31.  Gradients wrt space and coef are not computed. */
+int km_bilateral_blur_fwd(const void* x, const void* guide, const void* space, const void* coef, void* y, void* wsum, int B, int C, int Cg, int H,
+                          int W, int Bs, int Bc, int ky, int kx, int border, int dist, int dtype, void* stream);
+int km_bilateral_blur_bwd(const void* x, const void* guide, const void* space, const void* coef, const void* y, const void* wsum, const void* gy,
+                          void* gx, void* gguide, int B, int C, int Cg, int H, int W, int Bs, int Bc, int ky, int kx, int border, int dist, int dtype,
+                          void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,13 +11,17 @@ PyTorch/CPU fallback: tensors must be on a HIP device and the library must be bu
 from . import augmentation, core, enhance, filters, geometry, graph
 from ._native import NativeLibraryError, is_built, library_path
 from .filters import (
+    BilateralBlur,
     GaussianBlur2d,
+    JointBilateralBlur,
     MedianBlur,
     Sobel,
     SpatialGradient,
+    bilateral_blur,
     filter2d,
     filter2d_separable,
     gaussian_blur2d,
+    joint_bilateral_blur,
     median_blur,
     sobel,
     spatial_gradient,

@@ -81,10 +81,13 @@ _PROTOTYPES = {
     "km_median_blur_supported": [_I, _I, _I],
     "km_median_blur_fwd": [_P] * 4 + [_I] * 7 + [_P],
     "km_median_blur_bwd": [_P] * 4 + [_I] * 7 + [_P],
+    # km_abi_features() bit 3
+    "km_bilateral_blur_fwd": [_P] * 6 + [_I] * 12 + [_P],
+    "km_bilateral_blur_bwd": [_P] * 9 + [_I] * 12 + [_P],
 }
-ABI_FEATURES = 7  # the km_abi_features() bits this binding calls
+ABI_FEATURES = 15  # the km_abi_features() bits this binding calls
 _FEATURE_SYMBOLS = {"km_warp2d_pair_fwd": 1, "km_perspective_params_chain_fwd": 1, "km_inverse_chain_fwd": 1, "km_crop_resize_fwd": 2,
-                    "km_median_blur_supported": 4, "km_median_blur_fwd": 4, "km_median_blur_bwd": 4}
+                    "km_median_blur_supported": 4, "km_median_blur_fwd": 4, "km_median_blur_bwd": 4, "km_bilateral_blur_fwd": 8, "km_bilateral_blur_bwd": 8}
 KM_MASK_CODES = {torch.bool: 0, torch.uint8: 1, torch.int32: 2, torch.int64: 3, torch.float32: 4, torch.bfloat16: 5, torch.float16: 6}
 
 _lib: Optional[ctypes.CDLL] = None

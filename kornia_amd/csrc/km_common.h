@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define KM_ABI_FEATURES 7  // km_abi_features(): bit 0 = km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd; bit 1 = km_crop_resize_fwd; bit 2 = km_median_blur_supported / _fwd / _bwd
+#define KM_ABI_FEATURES 15  // km_abi_features(): bit 0 = km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd; bit 1 = km_crop_resize_fwd; bit 2 = km_median_blur_supported / _fwd / _bwd; bit 3 = km_bilateral_blur_fwd / _bwd
 #define KM_ABI_VERSION 3  // include/kornia_amd.h, "Versioning": a library of version N exports the symbol sets of every version <= N
 
 // dtype codes of the C ABI (include/kornia_amd.h)
@@ -283,6 +283,16 @@ __device__ __forceinline__ float km_med3(float a, float b, float c) {
     return __builtin_amdgcn_fmed3f(a, b, c);
 #else
     return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c));
+#endif
+}
+
+// 2^x in ONE instruction (v_exp_f32: 1 ulp; results below the normal range come out as 0) - callers fold log2(e) into the argument.  The host
+// pass, and the host build of the kernels, use exp2f.
+__device__ __forceinline__ float km_exp2(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_exp2f(x);
+#else
+    return exp2f(x);
 #endif
 }
 

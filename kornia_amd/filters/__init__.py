@@ -1,3 +1,4 @@
+from .bilateral import BilateralBlur, JointBilateralBlur, bilateral_blur, joint_bilateral_blur
 from .blur import (
     BoxBlur,
     Laplacian,

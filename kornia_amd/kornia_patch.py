@@ -46,6 +46,9 @@ _NATIVE = {
     "kornia.filters.canny": {"canny": _f.canny},
     # one launch instead of the one-hot conv2d copy + torch.median; windows or dtypes the native op refuses stay on Kornia's own function
     "kornia.filters.median": {"median_blur": _f.median_blur},
+    # one launch instead of pad + two unfold copies + ~ten elementwise passes; what the native op refuses (a 17 x 17 window, more than 16
+    # channels, sigma tensors that need a gradient) stays on Kornia's own function
+    "kornia.filters.bilateral": {"bilateral_blur": _f.bilateral_blur, "joint_bilateral_blur": _f.joint_bilateral_blur},
     # fused colour kernels (the ColorJitter leg)
     "kornia.enhance.adjust": {
         "adjust_brightness_accumulative": _e.adjust_brightness_accumulative,
@@ -92,8 +95,37 @@ def _use_native_median(args, kwargs) -> bool:
     return isinstance(image, torch.Tensor) and image.dim() == 4 and supported(kernel_size, image.dtype)
 
 
+_BILATERAL_PARAMS = ("kernel_size", "sigma_color", "sigma_space", "border_type", "color_distance_type")
+
+
+def _use_native_bilateral(joint: bool):
+    """bilateral_blur / joint_bilateral_blur: device tensors, 4-D, and everything ``filters.bilateral.supported`` asks for; anything else -
+    a 17 x 17 window, an even size or a bad distance name (Kornia's own errors), a sigma tensor that needs a gradient, CPU tensors - falls
+    through to Kornia's function."""
+    names = ("input",) + (("guidance",) if joint else ()) + _BILATERAL_PARAMS
+
+    def accept(args, kwargs) -> bool:
+        from .filters.bilateral import supported
+
+        if not _use_native(args, kwargs) or len(args) > len(names) or any(k not in names for k in kwargs):
+            return False
+        call = dict(zip(names, args))
+        if any(k in call for k in kwargs):
+            return False
+        call.update(kwargs)
+        if any(k not in call for k in names[:-2]):
+            return False
+        return supported(call["input"], call.get("guidance"), call["kernel_size"], call["sigma_color"], call["sigma_space"],
+                         call.get("border_type", "reflect"), call.get("color_distance_type", "l1"))
+
+    return accept
+
+
 def _dispatcher(original: Callable, native: Callable) -> Callable:
-    accept = _use_native_color if id(native) in _COLOR_OPS else (_use_native_median if native is _f.median_blur else _use_native)
+    if native is _f.bilateral_blur or native is _f.joint_bilateral_blur:
+        accept = _use_native_bilateral(native is _f.joint_bilateral_blur)
+    else:
+        accept = _use_native_color if id(native) in _COLOR_OPS else (_use_native_median if native is _f.median_blur else _use_native)
 
     @functools.wraps(original)
     def wrapper(*args, **kwargs):
