@@ -160,12 +160,8 @@ int km_select_samples_fwd(const void* transformed, const void* original, const v
     KM_REQUIRE(transformed && original && apply && out, "km_select_samples_fwd: null pointer");
     KM_REQUIRE(B > 0 && n_per_sample > 0, "km_select_samples_fwd: bad sizes B=%d n=%lld", B, n_per_sample);
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return km_select_run<float>(transformed, original, apply, out, B, (size_t)n_per_sample, s);
-        case KM_BF16: return km_select_run<km_bf16>(transformed, original, apply, out, B, (size_t)n_per_sample, s);
-        case KM_F16: return km_select_run<km_f16>(transformed, original, apply, out, B, (size_t)n_per_sample, s);
-        default: km_set_error("km_select_samples_fwd: dtype must be f32 / bf16 / f16"); return -1;
-    }
+    KM_REQUIRE(dtype == KM_F32 || dtype == KM_BF16 || dtype == KM_F16, "km_select_samples_fwd: dtype must be f32 / bf16 / f16");
+    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_select_run<KM_TAG_T(t)>(transformed, original, apply, out, B, (size_t)n_per_sample, s); });
 }
 
 // brightness / contrast / saturation / hue factors (B) fp32 on the device as ColorJitter's generator samples them (hue in turns),

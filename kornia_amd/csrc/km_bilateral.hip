@@ -512,12 +512,7 @@ int km_bilateral_blur_fwd(const void* x, const void* guide, const void* space, c
     if (kmb_check_pad(who, H, W, ky, kx, border) != 0) return -1;
     KM_REQUIRE(x && space && coef && y, "%s: null pointer", who);
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return kmb_fwd<float>(x, guide, space, coef, y, wsum, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, s);
-        case KM_F64: return kmb_fwd<double>(x, guide, space, coef, y, wsum, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, s);
-        case KM_BF16: return kmb_fwd<km_bf16>(x, guide, space, coef, y, wsum, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, s);
-        default: return kmb_fwd<km_f16>(x, guide, space, coef, y, wsum, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, s);
-    }
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmb_fwd<KM_TAG_T(t)>(x, guide, space, coef, y, wsum, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, s); });
 }
 
 int km_bilateral_blur_bwd(const void* x, const void* guide, const void* space, const void* coef, const void* y, const void* wsum, const void* gy, void* gx,
@@ -529,12 +524,7 @@ int km_bilateral_blur_bwd(const void* x, const void* guide, const void* space, c
     KM_REQUIRE(x && space && coef && y && wsum && gy, "%s: null pointer", who);
     KM_REQUIRE(guide ? (gx || gguide) : (gx && !gguide), "%s: self-guided takes gx alone, joint at least one of gx and gguide", who);
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return kmb_bwd<float>(x, guide, space, coef, y, wsum, gy, gx, gguide, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, s);
-        case KM_F64: return kmb_bwd<double>(x, guide, space, coef, y, wsum, gy, gx, gguide, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, s);
-        case KM_BF16: return kmb_bwd<km_bf16>(x, guide, space, coef, y, wsum, gy, gx, gguide, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, s);
-        default: return kmb_bwd<km_f16>(x, guide, space, coef, y, wsum, gy, gx, gguide, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, s);
-    }
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmb_bwd<KM_TAG_T(t)>(x, guide, space, coef, y, wsum, gy, gx, gguide, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, s); });
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@
 // W >= 8, H >= K, 16-byte aligned planes.  Everything else takes the generic LDS kernel.
 #include <stdlib.h>
 
+#include "km_filter_host.h"
 #include "km_regtile.h"
 
 
@@ -383,9 +384,5 @@ int km_blur_fast_bwd_supported(const void* gy, const void* gx, int H, int W, int
 
 int km_blur_fast_run(bool bwd, const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk, int K,
                      int border, int dtype, hipStream_t s) {
-    switch (dtype) {
-        case KM_F32: return km_blur_run<float>(bwd, x, kx, ky, y, B, C, H, W, Bk, K, border, s);
-        case KM_BF16: return km_blur_run<km_bf16>(bwd, x, kx, ky, y, B, C, H, W, Bk, K, border, s);
-        default: return km_blur_run<km_f16>(bwd, x, kx, ky, y, B, C, H, W, Bk, K, border, s);
-    }
+    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_blur_run<KM_TAG_T(t)>(bwd, x, kx, ky, y, B, C, H, W, Bk, K, border, s); });
 }

@@ -351,12 +351,8 @@ static int kmc_entry(const void* x, void* y, const void* params, double* gray_su
     }
     KM_REQUIRE(n_contrast <= 1, "km_color_jitter_fwd: at most one contrast stage");
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return kmc_run<float>(x, y, params, gray_sum, enable, apply, stages, n_stages, B, H, W, s);
-        case KM_BF16: return kmc_run<km_bf16>(x, y, params, gray_sum, enable, apply, stages, n_stages, B, H, W, s);
-        case KM_F16: return kmc_run<km_f16>(x, y, params, gray_sum, enable, apply, stages, n_stages, B, H, W, s);
-        default: km_set_error("km_color_jitter_fwd: dtype must be f32 / bf16 / f16"); return -1;
-    }
+    KM_REQUIRE(dtype == KM_F32 || dtype == KM_BF16 || dtype == KM_F16, "km_color_jitter_fwd: dtype must be f32 / bf16 / f16");
+    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmc_run<KM_TAG_T(t)>(x, y, params, gray_sum, enable, apply, stages, n_stages, B, H, W, s); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -653,12 +649,8 @@ int km_color_jitter_bwd(const void* x, const void* gy, void* gx, const void* par
     }
     KM_REQUIRE(n_contrast <= 1, "km_color_jitter_bwd: at most one contrast stage");
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return kmc_bwd_run<float>(x, gy, gx, params, gray_sum, gsum, gparams, enable, apply, stages, n_stages, B, H, W, s);
-        case KM_BF16: return kmc_bwd_run<km_bf16>(x, gy, gx, params, gray_sum, gsum, gparams, enable, apply, stages, n_stages, B, H, W, s);
-        case KM_F16: return kmc_bwd_run<km_f16>(x, gy, gx, params, gray_sum, gsum, gparams, enable, apply, stages, n_stages, B, H, W, s);
-        default: km_set_error("km_color_jitter_bwd: dtype must be f32 / bf16 / f16"); return -1;
-    }
+    KM_REQUIRE(dtype == KM_F32 || dtype == KM_BF16 || dtype == KM_F16, "km_color_jitter_bwd: dtype must be f32 / bf16 / f16");
+    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmc_bwd_run<KM_TAG_T(t)>(x, gy, gx, params, gray_sum, gsum, gparams, enable, apply, stages, n_stages, B, H, W, s); });
 }
 
 }  // extern "C"

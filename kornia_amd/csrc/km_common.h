@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define KM_ABI_FEATURES 15  // km_abi_features(): bit 0 = km_warp2d_pair_fwd, km_perspective_params_chain_fwd, km_inverse_chain_fwd; bit 1 = km_crop_resize_fwd; bit 2 = km_median_blur_supported / _fwd / _bwd; bit 3 = km_bilateral_blur_fwd / _bwd
 #define KM_ABI_VERSION 3  // include/kornia_amd.h, "Versioning": a library of version N exports the symbol sets of every version <= N
 
@@ -125,6 +127,30 @@ struct KmTraits<km_f16> {
     typedef float R;
     static constexpr int code = KM_F16;
 };
+
+// ---- run-time code -> compile-time argument (host) ------------------------------------------------
+// km_dispatch_dtype<float, km_bf16, km_f16>(dtype, other, f): f(KmType<T>()) for the listed T whose KmTraits<T>::code is `dtype` - the
+// list is exactly what the site instantiates -, `other` for a code that is not in the list.  In f: `typedef KM_TAG_T(t) T;`.
+// Plain templates and a generic lambda: inlined into the caller, nothing allocated.
+template <typename T>
+struct KmType {
+    typedef T type;
+};
+#define KM_TAG_T(tag) typename decltype(tag)::type
+template <typename T, typename... Ts, typename Ret, typename F>
+static inline Ret km_dispatch_dtype(int dtype, Ret other, F&& f) {
+    if (dtype == KmTraits<T>::code) return f(KmType<T>());
+    if constexpr (sizeof...(Ts) > 0) return km_dispatch_dtype<Ts...>(dtype, other, f);
+    else return other;
+}
+// the same for a list of int codes: f(std::integral_constant<int, CODE>()), a constant in f through `decltype(t)::value`
+// (km_dispatch_coord<KM_COORD_PERSPECTIVE, KM_COORD_AFFINE, KM_COORD_HOMOGRAPHY>(coord_mode, other, f) in the warp files)
+template <int V, int... Vs, typename Ret, typename F>
+static inline Ret km_dispatch_coord(int code, Ret other, F&& f) {
+    if (code == V) return f(std::integral_constant<int, V>());
+    if constexpr (sizeof...(Vs) > 0) return km_dispatch_coord<Vs...>(code, other, f);
+    else return other;
+}
 
 __device__ __forceinline__ float km_ld(const float* p) { return *p; }
 __device__ __forceinline__ double km_ld(const double* p) { return *p; }

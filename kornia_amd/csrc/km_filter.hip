@@ -19,6 +19,7 @@
 //   km_filter2d_bwd_kernel_kernel gradient wrt the taps (fp64 accumulation).
 #include <stdlib.h>
 
+#include "km_filter_host.h"
 #include "km_regtile.h"
 
 
@@ -531,35 +532,10 @@ static int km_full_frame_run(const void* gy, const void* k, void* gx, const KmFi
     return km_check_launch("km_filter2d_bwd_input(frame)");
 }
 
-// large separable kernels, forward (km_filter_sep_big.hip)
-int km_filter_sep_big_supported(int kH, int kW, int dtype);
-int km_filter_sep_big_run(const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk, int kH, int kW,
-                          int border, int same, int dtype, hipStream_t s);
-
-// register-tiled full kH x kW forward for square odd 3/5/7 kernels (km_filter2d_fast.hip)
-int km_filter2d_fast_tapgrad_run(const void* gy, const void* x, double* gk, int B, int C, int H, int W, int Bk, int K, int border, int dtype,
-                                 hipStream_t s);
-int km_filter2d_fast_supported(const void* x, const void* y, int H, int W, int kH, int kW, int border, int same, int dtype);
-int km_filter2d_fast_run(const void* x, const void* k, void* y, int B, int C, int H, int W, int Bk, int K, int border, int flip, int dtype,
-                         hipStream_t s);
-
-// register-tiled fast path for small square odd kernels (km_blur_fast.hip)
-int km_blur_fast_supported(const void* x, const void* y, int H, int W, int kH, int kW, int border, int same, int dtype);
-int km_blur_fast_bwd_supported(const void* gy, const void* gx, int H, int W, int kH, int kW, int border, int same, int dtype);
-int km_blur_fast_run(bool bwd, const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk, int K,
-                     int border, int dtype, hipStream_t s);
 static int km_sep_algo() {
     // KM_SEP_ALGO=lds forces the generic LDS-tiled kernels (debugging / A-B timing)
     return km_config().sep_lds;
 }
-
-#define KM_DISPATCH_DTYPE(dtype, CALL)                      \
-    switch (dtype) {                                        \
-        case KM_F32: return CALL(float);                    \
-        case KM_F64: return CALL(double);                   \
-        case KM_BF16: return CALL(km_bf16);                 \
-        default: return CALL(km_f16);                       \
-    }
 
 extern "C" {
 
@@ -573,9 +549,7 @@ int km_filter2d_fwd(const void* x, const void* k, void* y, int B, int C, int H, 
     if (km_sep_algo() == 0 && km_filter2d_fast_supported(x, y, H, W, kH, kW, border, same, dtype))
         return km_filter2d_fast_run(x, k, y, B, C, H, W, Bk, kH, border, 0, dtype, (hipStream_t)stream);
     const KmFilterGeom g = km_filter_geom(B, C, H, W, Bk, kH, kW, border, same);
-#define CALL(T) km_full_run<T>(0, x, nullptr, k, y, nullptr, g, (hipStream_t)stream)
-    KM_DISPATCH_DTYPE(dtype, CALL)
-#undef CALL
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(0, x, nullptr, k, y, nullptr, g, (hipStream_t)stream); });
 }
 
 // gradient wrt input (adjoint incl. the pad fold): gy (B,C,Ho,Wo) -> gx (B,C,H,W)
@@ -594,14 +568,10 @@ int km_filter2d_bwd_input(const void* gy, const void* k, void* gx, int B, int C,
         if (km_sep_algo() == 0 && km_filter2d_fast_supported(gy, gx, H, W, kH, kW, border, same, dtype) && H > 2 * pd && W > 2 * pd) {
             const int rc = km_filter2d_fast_run(gy, k, gx, B, C, H, W, Bk, kH, KM_BORDER_CONSTANT, 1, dtype, (hipStream_t)stream);
             if (rc != 0 || border == KM_BORDER_CONSTANT) return rc;
-#define CALLF(T) km_full_frame_run<T>(gy, k, gx, g, pd, (hipStream_t)stream)
-            KM_DISPATCH_DTYPE(dtype, CALLF)
-#undef CALLF
+            return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_frame_run<KM_TAG_T(t)>(gy, k, gx, g, pd, (hipStream_t)stream); });
         }
     }
-#define CALL(T) km_full_run<T>(1, nullptr, gy, k, gx, nullptr, g, (hipStream_t)stream)
-    KM_DISPATCH_DTYPE(dtype, CALL)
-#undef CALL
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(1, nullptr, gy, k, gx, nullptr, g, (hipStream_t)stream); });
 }
 
 // gradient wrt the prepared taps: gk (Bk,kH,kW) fp64, pre-zeroed
@@ -613,9 +583,7 @@ int km_filter2d_bwd_kernel(const void* gy, const void* x, void* gk, int B, int C
     if (km_sep_algo() == 0 && km_filter2d_fast_supported(x, gy, H, W, kH, kW, border, same, dtype))  // one pass instead of kH*kW
         return km_filter2d_fast_tapgrad_run(gy, x, (double*)gk, B, C, H, W, Bk, kH, border, dtype, (hipStream_t)stream);
     const KmFilterGeom g = km_filter_geom(B, C, H, W, Bk, kH, kW, border, same);
-#define CALL(T) km_full_run<T>(2, x, gy, nullptr, nullptr, (double*)gk, g, (hipStream_t)stream)
-    KM_DISPATCH_DTYPE(dtype, CALL)
-#undef CALL
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(2, x, gy, nullptr, nullptr, (double*)gk, g, (hipStream_t)stream); });
 }
 
 // Replaces filter2d_separable (filter.py:155-207): kx (Bk,kW), ky (Bk,kH) in the compute dtype.
@@ -629,9 +597,7 @@ int km_filter2d_sep_fwd(const void* x, const void* kx, const void* ky, void* y, 
     if (km_sep_algo() == 0 && km_filter_sep_big_supported(kH, kW, dtype))  // k >= 10: sliding-window LDS kernel
         return km_filter_sep_big_run(x, kx, ky, y, B, C, H, W, Bk, kH, kW, border, same, dtype, (hipStream_t)stream);
     const KmFilterGeom g = km_filter_geom(B, C, H, W, Bk, kH, kW, border, same);
-#define CALL(T) km_sep_run<T>(false, x, kx, ky, y, g, (hipStream_t)stream)
-    KM_DISPATCH_DTYPE(dtype, CALL)
-#undef CALL
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_sep_run<KM_TAG_T(t)>(false, x, kx, ky, y, g, (hipStream_t)stream); });
 }
 
 int km_filter2d_sep_bwd_input(const void* gy, const void* kx, const void* ky, void* gx, int B, int C, int H, int W, int Bk,
@@ -643,9 +609,7 @@ int km_filter2d_sep_bwd_input(const void* gy, const void* kx, const void* ky, vo
         return km_blur_fast_run(true, gy, kx, ky, gx, B, C, H, W, Bk, kH, border, dtype, (hipStream_t)stream);
     KM_REQUIRE(kH - 1 <= KM_FS_TH && kW - 1 <= KM_FS_TW, "km_filter2d_sep_bwd_input: kernel larger than the tile; use the generic path");
     const KmFilterGeom g = km_filter_geom(B, C, H, W, Bk, kH, kW, border, same);
-#define CALL(T) km_sep_run<T>(true, gy, kx, ky, gx, g, (hipStream_t)stream)
-    KM_DISPATCH_DTYPE(dtype, CALL)
-#undef CALL
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_sep_run<KM_TAG_T(t)>(true, gy, kx, ky, gx, g, (hipStream_t)stream); });
 }
 
 // Which fused separable kernels can take this kernel size (LDS budgets): bit 0 = forward (km_filter2d_sep_fwd),

@@ -8,6 +8,7 @@
 // (rows: wave-uniform address select; columns: per-lane halo indices computed once).  The fma chain runs in
 // (p, q) order from 0 over the whole kernel - bit-identical to oracle/ko_impl.h ko_filter2d_fwd.
 // HBM traffic = read x once + write y once = 2e bytes / element.
+#include "km_filter_host.h"
 #include "km_regtile.h"
 
 #define KMF_ROWS 32
@@ -249,11 +250,7 @@ static int kmf_tapgrad_run(const void* gy, const void* x, double* gk, int B, int
 
 int km_filter2d_fast_tapgrad_run(const void* gy, const void* x, double* gk, int B, int C, int H, int W, int Bk, int K, int border, int dtype,
                                  hipStream_t s) {
-    switch (dtype) {
-        case KM_F32: return kmf_tapgrad_run<float>(gy, x, gk, B, C, H, W, Bk, K, border, s);
-        case KM_BF16: return kmf_tapgrad_run<km_bf16>(gy, x, gk, B, C, H, W, Bk, K, border, s);
-        default: return kmf_tapgrad_run<km_f16>(gy, x, gk, B, C, H, W, Bk, K, border, s);
-    }
+    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmf_tapgrad_run<KM_TAG_T(t)>(gy, x, gk, B, C, H, W, Bk, K, border, s); });
 }
 
 // 1 if the register-tiled kernel handles this problem ('same', square odd 3/5/7, W % 4 == 0, 16-byte aligned, not fp64)
@@ -271,9 +268,5 @@ int km_filter2d_fast_supported(const void* x, const void* y, int H, int W, int k
 // border = constant that is the exact adjoint of the constant-padded correlation, and the interior of every other one.
 int km_filter2d_fast_run(const void* x, const void* k, void* y, int B, int C, int H, int W, int Bk, int K, int border, int flip, int dtype,
                          hipStream_t s) {
-    switch (dtype) {
-        case KM_F32: return kmf_run<float>(x, k, y, B, C, H, W, Bk, K, border, flip, s);
-        case KM_BF16: return kmf_run<km_bf16>(x, k, y, B, C, H, W, Bk, K, border, flip, s);
-        default: return kmf_run<km_f16>(x, k, y, B, C, H, W, Bk, K, border, flip, s);
-    }
+    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmf_run<KM_TAG_T(t)>(x, k, y, B, C, H, W, Bk, K, border, flip, s); });
 }

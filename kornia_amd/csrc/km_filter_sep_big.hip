@@ -10,6 +10,7 @@
 // taps = 32 fused multiply-adds from them - an LDS read per ~3-8 multiply-adds instead of per 1.  The taps are applied
 // in increasing order from 0, so the result is bit-identical to oracle/ko_impl.h (ko_filter2d_fwd twice).
 // HBM traffic: read x ~1.8x for k = 23 (halo, served mostly by L2) + write y once.
+#include "km_filter_host.h"
 #include "km_regtile.h"
 
 #define KMS_TW 64
@@ -224,9 +225,5 @@ static int kms_run(const void* x, const void* kx, const void* ky, void* y, int B
 
 int km_filter_sep_big_run(const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk, int kH, int kW,
                           int border, int same, int dtype, hipStream_t s) {
-    switch (dtype) {
-        case KM_F32: return kms_run<float>(x, kx, ky, y, B, C, H, W, Bk, kH, kW, border, same, s);
-        case KM_BF16: return kms_run<km_bf16>(x, kx, ky, y, B, C, H, W, Bk, kH, kW, border, same, s);
-        default: return kms_run<km_f16>(x, kx, ky, y, B, C, H, W, Bk, kH, kW, border, same, s);
-    }
+    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kms_run<KM_TAG_T(t)>(x, kx, ky, y, B, C, H, W, Bk, kH, kW, border, same, s); });
 }

@@ -403,12 +403,7 @@ int km_spatial_gradient_fwd(const void* x, const void* kern_host, void* out, voi
     KM_REQUIRE(x && kern_host && (out || mag), "km_spatial_gradient_fwd: null pointer");
     KM_REQUIRE(!mag || n_out == 2, "km_spatial_gradient_fwd: magnitude needs n_out == 2");
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return km_grad_run<float>(false, x, nullptr, kern_host, out, mag, B * C, H, W, n_out, kS, eps, s);
-        case KM_F64: return km_grad_run<double>(false, x, nullptr, kern_host, out, mag, B * C, H, W, n_out, kS, eps, s);
-        case KM_BF16: return km_grad_run<km_bf16>(false, x, nullptr, kern_host, out, mag, B * C, H, W, n_out, kS, eps, s);
-        default: return km_grad_run<km_f16>(false, x, nullptr, kern_host, out, mag, B * C, H, W, n_out, kS, eps, s);
-    }
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_grad_run<KM_TAG_T(t)>(false, x, nullptr, kern_host, out, mag, B * C, H, W, n_out, kS, eps, s); });
 }
 
 // gout: (B,C,n_out,H,W) -> gx: (B,C,H,W)
@@ -418,12 +413,7 @@ int km_spatial_gradient_bwd(const void* gout, const void* kern_host, void* gx, i
     if (km_grad_validate("km_spatial_gradient_bwd", B, C, H, W, n_out, kS, dtype)) return -1;
     KM_REQUIRE(gout && kern_host && gx, "km_spatial_gradient_bwd: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return km_grad_run<float>(true, nullptr, gout, kern_host, gx, nullptr, B * C, H, W, n_out, kS, 0.0, s);
-        case KM_F64: return km_grad_run<double>(true, nullptr, gout, kern_host, gx, nullptr, B * C, H, W, n_out, kS, 0.0, s);
-        case KM_BF16: return km_grad_run<km_bf16>(true, nullptr, gout, kern_host, gx, nullptr, B * C, H, W, n_out, kS, 0.0, s);
-        default: return km_grad_run<km_f16>(true, nullptr, gout, kern_host, gx, nullptr, B * C, H, W, n_out, kS, 0.0, s);
-    }
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_grad_run<KM_TAG_T(t)>(true, nullptr, gout, kern_host, gx, nullptr, B * C, H, W, n_out, kS, 0.0, s); });
 }
 
 }  // extern "C"

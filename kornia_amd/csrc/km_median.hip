@@ -354,12 +354,7 @@ int km_median_blur_fwd(const void* x, void* y, void* idx, const void* apply, int
     if ((uint64_t)B * C * H * W == 0) return 0;
     KM_REQUIRE(x && y, "km_median_blur_fwd: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return kmm_fwd<float>(x, y, idx, apply, B, C, H, W, ky, kx, s);
-        case KM_F64: return kmm_fwd<double>(x, y, idx, apply, B, C, H, W, ky, kx, s);
-        case KM_BF16: return kmm_fwd<km_bf16>(x, y, idx, apply, B, C, H, W, ky, kx, s);
-        default: return kmm_fwd<km_f16>(x, y, idx, apply, B, C, H, W, ky, kx, s);
-    }
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmm_fwd<KM_TAG_T(t)>(x, y, idx, apply, B, C, H, W, ky, kx, s); });
 }
 
 int km_median_blur_bwd(const void* gy, const void* idx, const void* apply, void* gx, int B, int C, int H, int W, int ky, int kx, int dtype, void* stream) {
@@ -369,12 +364,7 @@ int km_median_blur_bwd(const void* gy, const void* idx, const void* apply, void*
     if ((uint64_t)B * C * H * W == 0) return 0;
     KM_REQUIRE(gy && idx && gx, "km_median_blur_bwd: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return kmm_bwd<float>(gy, idx, apply, gx, B, C, H, W, ky, kx, s);
-        case KM_F64: return kmm_bwd<double>(gy, idx, apply, gx, B, C, H, W, ky, kx, s);
-        case KM_BF16: return kmm_bwd<km_bf16>(gy, idx, apply, gx, B, C, H, W, ky, kx, s);
-        default: return kmm_bwd<km_f16>(gy, idx, apply, gx, B, C, H, W, ky, kx, s);
-    }
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmm_bwd<KM_TAG_T(t)>(gy, idx, apply, gx, B, C, H, W, ky, kx, s); });
 }
 
 }  // extern "C"

@@ -534,12 +534,7 @@ static int kmp_validate(const char* what, const void* x, const void* y, int B, i
 }
 
 static int kmp_dispatch(bool blur, const void* x, void* y, int B, int C, int H, int W, int oh, int ow, int border, int align, int dtype, hipStream_t s) {
-    switch (dtype) {
-        case KM_F32: return kmp_run<float>(blur, x, y, B, C, H, W, oh, ow, border, align, s);
-        case KM_F64: return kmp_run<double>(blur, x, y, B, C, H, W, oh, ow, border, align, s);
-        case KM_BF16: return kmp_run<km_bf16>(blur, x, y, B, C, H, W, oh, ow, border, align, s);
-        default: return kmp_run<km_f16>(blur, x, y, B, C, H, W, oh, ow, border, align, s);
-    }
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmp_run<KM_TAG_T(t)>(blur, x, y, B, C, H, W, oh, ow, border, align, s); });
 }
 
 extern "C" {
@@ -551,11 +546,7 @@ int km_pyrdown_fwd(const void* x, void* y, int B, int C, int H, int W, int oh, i
     KM_REQUIRE(border != KM_BORDER_REFLECT || (H > 2 && W > 2), "km_pyrdown_fwd: reflect padding needs H, W > 2 (got %dx%d)", H, W);
     if ((uint64_t)B * C * oh * ow == 0) return 0;
     if (kmp_fast_ok(x, y, H, W, oh, ow, align, dtype)) {
-        switch (dtype) {
-            case KM_F32: return kmp_run2<float>(x, y, B, C, H, W, border, (hipStream_t)stream);
-            case KM_BF16: return kmp_run2<km_bf16>(x, y, B, C, H, W, border, (hipStream_t)stream);
-            default: return kmp_run2<km_f16>(x, y, B, C, H, W, border, (hipStream_t)stream);
-        }
+        return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmp_run2<KM_TAG_T(t)>(x, y, B, C, H, W, border, (hipStream_t)stream); });
     }
     return kmp_dispatch(true, x, y, B, C, H, W, oh, ow, border, align ? 1 : 0, dtype, (hipStream_t)stream);
 }
@@ -564,11 +555,7 @@ int km_resize_bilinear_fwd(const void* x, void* y, int B, int C, int H, int W, i
     if (kmp_validate("km_resize_bilinear_fwd", x, y, B, C, H, W, oh, ow, dtype)) return -1;
     if ((uint64_t)B * C * oh * ow == 0) return 0;
     if (kmp_up2_ok(x, y, H, W, oh, ow, align, dtype)) {
-        switch (dtype) {
-            case KM_F32: return kmp_run_up2<float>(x, y, B, C, H, W, (hipStream_t)stream);
-            case KM_BF16: return kmp_run_up2<km_bf16>(x, y, B, C, H, W, (hipStream_t)stream);
-            default: return kmp_run_up2<km_f16>(x, y, B, C, H, W, (hipStream_t)stream);
-        }
+        return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmp_run_up2<KM_TAG_T(t)>(x, y, B, C, H, W, (hipStream_t)stream); });
     }
     return kmp_dispatch(false, x, y, B, C, H, W, oh, ow, 0, align ? 1 : 0, dtype, (hipStream_t)stream);
 }
@@ -581,12 +568,7 @@ int km_resize_bilinear_bwd(const void* gy, void* gx, int B, int C, int H, int W,
     if ((uint64_t)B * C == 0) return 0;
     KM_REQUIRE(gy && gx, "km_resize_bilinear_bwd: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return kmp_run_resize_bwd<float>(gy, gx, B, C, H, W, oh, ow, align ? 1 : 0, s);
-        case KM_F64: return kmp_run_resize_bwd<double>(gy, gx, B, C, H, W, oh, ow, align ? 1 : 0, s);
-        case KM_BF16: return kmp_run_resize_bwd<km_bf16>(gy, gx, B, C, H, W, oh, ow, align ? 1 : 0, s);
-        default: return kmp_run_resize_bwd<km_f16>(gy, gx, B, C, H, W, oh, ow, align ? 1 : 0, s);
-    }
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmp_run_resize_bwd<KM_TAG_T(t)>(gy, gx, B, C, H, W, oh, ow, align ? 1 : 0, s); });
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "km_warp_args.h"
+#include "km_warp_host.h"
 #include "km_warp_stage.h"
 
 #define KM_ROWS 4   // output rows per thread
@@ -958,9 +959,6 @@ __global__ __launch_bounds__(256, KMB_WAVES_PER_EU) void km_warp_fwd_box_kernel(
     kmb_region<T, CM, NC, ALIGN, STREAM>(a, km_xcd_remap(blockIdx.x, a.nblocks, a.reverse), s_rv, s_info, s_src);
 }
 
-// LDS-staged bicubic forward (km_warp_cubic.hip): launches and returns 1 when it takes the case, 0 otherwise
-int km_warp_fwd_cubic_try_any(int dtype, int coord_mode, const void* args, hipStream_t s);
-
 // the specialised forward: bilinear + zeros, fp32 compute, 32-bit byte offsets inside a plane, 24-bit row / column counts
 template <typename T, int CM>
 static bool km_fwd_lean_ok(const KmWarpArgs<T>& a) {
@@ -1001,12 +999,8 @@ template <typename T>
 static uint64_t km_warp_fwd_box_blocks(const KmWarpArgs<T>& a) {
     return (uint64_t)((a.g.w + KmbWide::TW - 1) / KmbWide::TW) * (uint64_t)((a.g.h + KmbWide::TH - 1) / KmbWide::TH) * (uint64_t)a.g.B;
 }
-#ifndef KM_FWD_BOX_DEFAULT
-#define KM_FWD_BOX_DEFAULT 1      // fp32 storage: the box forward is what the hot configuration runs (KM_WARP_FWD_ALGO=rows: the gather kernel)
-#endif
-#ifndef KM_FWD_BOX_DEFAULT_16
-#define KM_FWD_BOX_DEFAULT_16 1   // 16-bit storage (config 3, 224^2 bf16 under +-15 degrees: 97 -> 73 us through the square tiles)
-#endif
+// The box forward is what the hot configuration runs (KM_WARP_FWD_ALGO=rows: the gather kernel), for fp32 and for 16-bit storage
+// (config 3, 224^2 bf16 under +-15 degrees: 97 -> 73 us through the square tiles).
 template <typename T, int CM>
 static void km_warp_fwd_lean_launch(const KmWarpArgs<T>& a, hipStream_t s) {
     if constexpr (CM != KM_COORD_GRID && sizeof(typename KmTraits<T>::R) == sizeof(float)) {  // (never instantiated otherwise)
@@ -1016,7 +1010,7 @@ static void km_warp_fwd_lean_launch(const KmWarpArgs<T>& a, hipStream_t s) {
             // (an output with fewer pixels than the source is, as a rule, a map that MINIFIES - warp to a smaller dsize: the boxes would not fit
             // and the kernel would end in its gather rows after paying for the attempt, 7 - 10 % behind the gather kernel; that one is launched then)
             const bool shrinks = (uint64_t)a.g.H * (uint64_t)a.g.W * 10u > (uint64_t)a.g.h * (uint64_t)a.g.w * 13u;
-            const bool want_box = algo == 3 || ((sizeof(T) == 2 ? KM_FWD_BOX_DEFAULT_16 : KM_FWD_BOX_DEFAULT) && algo == 0 && !shrinks);
+            const bool want_box = algo == 3 || (algo == 0 && !shrinks);
             if (want_box && (a.g.C == 3 || a.g.C == 1) && (a.g.W & 3) == 0 && ((uintptr_t)a.src % (4 * sizeof(T))) == 0 && nbb < (1ull << 31)) {
                 if (a.g.C == 3) km_warp_fwd_box_launch_nc<T, CM, 3>(a, s);
                 else km_warp_fwd_box_launch_nc<T, CM, 1>(a, s);
@@ -1027,6 +1021,13 @@ static void km_warp_fwd_lean_launch(const KmWarpArgs<T>& a, hipStream_t s) {
         else if (a.g.C == 1) km_warp_fwd_lean_launch_nc<T, CM, 1>(a, s);
         else km_warp_fwd_lean_launch_nc<T, CM, 0>(a, s);
     }
+}
+
+// the LDS-staged bicubic forward (km_warp_cubic.hip) where it exists: matrices, fp32 compute (fp64 computes in double: the generic kernel)
+template <typename T, int CM>
+static bool km_fwd_cubic_try(const KmWarpArgs<T>& a, hipStream_t s) {
+    if constexpr (CM == KM_COORD_GRID || sizeof(typename KmTraits<T>::R) != sizeof(float)) return false;
+    else return km_warp_fwd_cubic_try_any(a, CM, s) != 0;
 }
 
 template <typename T, int CM, int INTERP>
@@ -1042,7 +1043,7 @@ static int km_warp_launch(bool bwd, const KmWarpArgs<T>& a, hipStream_t s) {
             hipLaunchKernelGGL((km_warp_fwd_bz_kernel<T, CM, 1>), dim3(a.nblocks), dim3(256), 0, s, a);
         else
             hipLaunchKernelGGL((km_warp_fwd_bz_kernel<T, CM, 0>), dim3(a.nblocks), dim3(256), 0, s, a);
-    } else if (INTERP == KM_INTERP_BICUBIC && !km_fwd_generic_forced() && km_warp_fwd_cubic_try_any(KmTraits<T>::code, CM, &a, s)) {
+    } else if (INTERP == KM_INTERP_BICUBIC && !km_fwd_generic_forced() && km_fwd_cubic_try<T, CM>(a, s)) {
     } else
         hipLaunchKernelGGL((km_warp_fwd_kernel<T, CM, INTERP>), dim3(a.nblocks), dim3(256), 0, s, a);
     return km_check_launch(bwd ? "km_warp2d_bwd" : "km_warp2d_fwd");
@@ -1057,71 +1058,68 @@ static int km_warp_dispatch_interp(bool bwd, const KmWarpArgs<T>& a, hipStream_t
     }
 }
 
+
+
 template <typename T>
-static int km_warp_run(bool bwd, const void* src, const void* mat, void* dst, const void* gout, void* gsrc, double* gmat,
-                       int B, int C, int H, int W, int h, int w, int B_M, int coord_mode, int norm_coords, int interp,
-                       int pad, int align, const void* fill, hipStream_t s, const void* grid = nullptr, void* ggrid = nullptr,
-                       const void* apply = nullptr) {
+static int km_warp_run(bool bwd, const KmWarpCall& c) {
     typedef typename KmTraits<T>::R R;
     KmWarpArgs<T> a;
-    a.apply = (const uint8_t*)apply;
-    a.src = (const T*)src;
-    a.mat = (const R*)mat;
-    a.dst = (T*)dst;
-    a.gout = (const T*)gout;
-    a.gsrc = (R*)gsrc;
-    a.gmat = gmat;
-    a.fill = (const R*)fill;
-    a.grid = (const T*)grid;
-    a.ggrid = (R*)ggrid;
-    KmWarpGeom<R>& g = a.g;
-    km_geom_init(g, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align);
-    a.tiles_x = (uint32_t)((w + KM_TILE_W - 1) / KM_TILE_W);
-    a.tiles_y = (uint32_t)((h + KM_TILE_H - 1) / KM_TILE_H);
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B;
+    a.apply = (const uint8_t*)c.apply;
+    a.src = (const T*)c.src;
+    a.mat = (const R*)c.mat;
+    a.dst = (T*)c.dst;
+    a.gout = (const T*)c.gout;
+    a.gsrc = (R*)c.gsrc;
+    a.gmat = c.gmat;
+    a.fill = (const R*)c.fill;
+    a.grid = (const T*)c.grid;
+    a.ggrid = (R*)c.ggrid;
+    km_geom_init(a.g, c);
+    a.tiles_x = (uint32_t)((c.w + KM_TILE_W - 1) / KM_TILE_W);
+    a.tiles_y = (uint32_t)((c.h + KM_TILE_H - 1) / KM_TILE_H);
+    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)c.B;
     KM_REQUIRE(nb < (1ull << 31), "km_warp2d: grid too large (%llu blocks)", (unsigned long long)nb);
     a.nblocks = (uint32_t)nb;
     a.reverse = 0;
     a.stream_out = 0;
     if (nb == 0) return 0;
-    switch (coord_mode) {
-        case KM_COORD_PERSPECTIVE: return km_warp_dispatch_interp<T, KM_COORD_PERSPECTIVE>(bwd, a, s);
-        case KM_COORD_AFFINE: return km_warp_dispatch_interp<T, KM_COORD_AFFINE>(bwd, a, s);
-        case KM_COORD_GRID: return km_warp_dispatch_interp<T, KM_COORD_GRID>(bwd, a, s);
-        default: return km_warp_dispatch_interp<T, KM_COORD_HOMOGRAPHY>(bwd, a, s);
-    }
+    return km_dispatch_coord<KM_COORD_PERSPECTIVE, KM_COORD_AFFINE, KM_COORD_GRID, KM_COORD_HOMOGRAPHY>(
+        c.coord_mode, -1, [&](auto cm) { return km_warp_dispatch_interp<T, decltype(cm)::value>(bwd, a, c.stream); });
 }
 
-static int km_warp_validate(const char* fn, const void* src, const void* mat, int B, int C, int H, int W, int h, int w,
-                            int B_M, int coord_mode, int interp, int pad, const void* fill, int dtype) {
-    KM_REQUIRE(src && mat, "%s: null pointer", fn);  // (grid mode passes the grid as `mat`)
-    KM_REQUIRE(B >= 0 && C >= 0 && H > 0 && W > 0 && h >= 0 && w >= 0, "%s: bad shape B=%d C=%d H=%d W=%d h=%d w=%d", fn, B, C, H, W, h, w);
-    KM_REQUIRE((int64_t)H * W < (1ll << 31) && (int64_t)h * w < (1ll << 31), "%s: image plane exceeds 2^31 elements", fn);
-    KM_REQUIRE(B_M == 1 || B_M == B, "%s: matrix batch %d must be 1 or %d", fn, B_M, B);
-    KM_REQUIRE(coord_mode >= 0 && coord_mode <= 2, "%s: bad coord_mode %d", fn, coord_mode);
-    KM_REQUIRE(interp >= 0 && interp <= 2, "%s: bad interp %d", fn, interp);
-    KM_REQUIRE(pad >= 0 && pad <= 3, "%s: bad pad %d", fn, pad);
-    KM_REQUIRE(pad != KM_PAD_FILL || fill, "%s: pad=fill needs fill values", fn);
-    KM_REQUIRE(dtype >= 0 && dtype <= 3, "%s: bad dtype %d", fn, dtype);
+// the generic kernels (and, forward, the specialised ones behind them) in the call's storage type
+static int km_warp_run_any(bool bwd, const KmWarpCall& c) {
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(c.dtype, -1, [&](auto t) { return km_warp_run<KM_TAG_T(t)>(bwd, c); });
+}
+
+static int km_warp_validate(const char* fn, const KmWarpCall& c) {
+    KM_REQUIRE(c.src && c.mat, "%s: null pointer", fn);  // (grid mode passes the grid as `mat`)
+    KM_REQUIRE(c.B >= 0 && c.C >= 0 && c.H > 0 && c.W > 0 && c.h >= 0 && c.w >= 0, "%s: bad shape B=%d C=%d H=%d W=%d h=%d w=%d", fn, c.B, c.C, c.H, c.W, c.h, c.w);
+    KM_REQUIRE((int64_t)c.H * c.W < (1ll << 31) && (int64_t)c.h * c.w < (1ll << 31), "%s: image plane exceeds 2^31 elements", fn);
+    KM_REQUIRE(c.B_M == 1 || c.B_M == c.B, "%s: matrix batch %d must be 1 or %d", fn, c.B_M, c.B);
+    // (KM_COORD_GRID is not a mode a caller names: the grid entry points set it, together with the grid)
+    KM_REQUIRE((c.coord_mode >= 0 && c.coord_mode <= 2) || (c.coord_mode == KM_COORD_GRID && c.grid), "%s: bad coord_mode %d", fn, c.coord_mode);
+    KM_REQUIRE(c.interp >= 0 && c.interp <= 2, "%s: bad interp %d", fn, c.interp);
+    KM_REQUIRE(c.pad >= 0 && c.pad <= 3, "%s: bad pad %d", fn, c.pad);
+    KM_REQUIRE(c.pad != KM_PAD_FILL || c.fill, "%s: pad=fill needs fill values", fn);
+    KM_REQUIRE(c.dtype >= 0 && c.dtype <= 3, "%s: bad dtype %d", fn, c.dtype);
     return 0;
 }
 
-// owner-computes grad_src for bilinear + zeros/fill (km_warp_bwd_tiled.hip)
-int km_warp_bwd_tiled_supported(int interp, int pad, int dtype, const void* gsrc);
-int km_warp_bwd_tiled_dims_ok(int h, int w);
-int km_warp_bwd_tiled_run(const void* gout, const void* mat, void* gsrc, int B, int C, int H, int W, int h, int w, int B_M, int coord_mode, int norm_coords,
-                          int pad, int align, int dtype, hipStream_t s);
+// km_warp2d_fwd (apply == nullptr) and km_warp2d_fwd_masked
+int km_warp_fwd_call(const char* fn, const KmWarpCall& c) {
+    if (c.B == 0 || c.C == 0 || c.h == 0 || c.w == 0) return 0;  // empty output
+    if (km_warp_validate(fn, c)) return -1;
+    KM_REQUIRE(c.dst, "%s: null dst", fn);
+    KM_REQUIRE(!c.apply || (c.h == c.H && c.w == c.W), "%s: a per-sample switch needs equal source and destination sizes (%dx%d -> %dx%d)", fn, c.H, c.W, c.h, c.w);
+    return km_warp_run_any(false, c);
+}
 
-// matrix gradient of the bilinear warps (km_warp_gm.hip)
-int km_warp_gm_supported(int interp, int pad, int dtype, int H, int W, int h, int w);
-int km_warp_gm_run(const void* gout, const void* src, const void* mat, double* gmat, int B, int C, int H, int W, int h, int w, int B_M,
-                   int coord_mode, int norm_coords, int pad, int align, const void* fill, int dtype, hipStream_t s);
-
-// both gradients from one read of grad_out (km_warp_bwd_fused.hip)
-int km_warp_bwd_fused_supported(int interp, int pad, int dtype, int C, int H, int W, int h, int w);
-size_t km_warp_bwd_fused_workspace(int B, int C, int H, int W);
-int km_warp_bwd_fused_run(const void* gout, const void* src, const void* mat, void* gsrc, double* gmat, void* ws, int B, int C, int H, int W, int h, int w,
-                          int B_M, int coord_mode, int norm_coords, int pad, int align, const void* fill, int dtype, hipStream_t s);
+// the one-read backward (km_warp_bwd_fused.hip) can take the call with this workspace
+static bool km_bwd_one_read_ok(const KmWarpCall& c, const void* workspace, long long workspace_bytes) {
+    return workspace && km_warp_bwd_fused_supported(c) && (unsigned long long)workspace_bytes >= (unsigned long long)km_warp_bwd_fused_workspace(c) &&
+           ((uintptr_t)workspace & 15) == 0;
+}
 
 extern "C" {
 
@@ -1131,33 +1129,24 @@ extern "C" {
 int km_warp2d_fwd(const void* src, const void* mat, void* dst, int B, int C, int H, int W, int h, int w, int B_M,
                   int coord_mode, int norm_coords, int interp, int pad, int align, const void* fill, int dtype,
                   void* stream) {
-    if (B == 0 || C == 0 || h == 0 || w == 0) return 0;  // empty output
-    if (km_warp_validate("km_warp2d_fwd", src, mat, B, C, H, W, h, w, B_M, coord_mode, interp, pad, fill, dtype)) return -1;
-    KM_REQUIRE(dst, "km_warp2d_fwd: null dst");
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return km_warp_run<float>(false, src, mat, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s);
-        case KM_F64: return km_warp_run<double>(false, src, mat, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s);
-        case KM_BF16: return km_warp_run<km_bf16>(false, src, mat, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s);
-        default: return km_warp_run<km_f16>(false, src, mat, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s);
-    }
+    KmWarpCall c;
+    c.src = src; c.mat = mat; c.dst = dst; c.fill = fill;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.h = h; c.w = w; c.B_M = B_M;
+    c.coord_mode = coord_mode; c.norm_coords = norm_coords; c.interp = interp; c.pad = pad; c.align = align; c.dtype = dtype;
+    c.stream = (hipStream_t)stream;
+    return km_warp_fwd_call("km_warp2d_fwd", c);
 }
 
 // km_warp2d_fwd with the augmentation layer's per-sample switch folded in (kornia/augmentation/base.py:348-393): apply (B) uint8 on
 // the device; a sample whose entry is 0 is copied instead of warped.  Needs h == H and w == W (what torch.where needs too).
 int km_warp2d_fwd_masked(const void* src, const void* mat, void* dst, const void* apply, int B, int C, int H, int W, int h, int w, int B_M,
                          int coord_mode, int norm_coords, int interp, int pad, int align, const void* fill, int dtype, void* stream) {
-    if (B == 0 || C == 0 || h == 0 || w == 0) return 0;  // empty output
-    if (km_warp_validate("km_warp2d_fwd_masked", src, mat, B, C, H, W, h, w, B_M, coord_mode, interp, pad, fill, dtype)) return -1;
-    KM_REQUIRE(dst, "km_warp2d_fwd_masked: null dst");
-    KM_REQUIRE(!apply || (h == H && w == W), "km_warp2d_fwd_masked: a per-sample switch needs equal source and destination sizes (%dx%d -> %dx%d)", H, W, h, w);
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return km_warp_run<float>(false, src, mat, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s, nullptr, nullptr, apply);
-        case KM_F64: return km_warp_run<double>(false, src, mat, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s, nullptr, nullptr, apply);
-        case KM_BF16: return km_warp_run<km_bf16>(false, src, mat, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s, nullptr, nullptr, apply);
-        default: return km_warp_run<km_f16>(false, src, mat, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s, nullptr, nullptr, apply);
-    }
+    KmWarpCall c;
+    c.src = src; c.mat = mat; c.dst = dst; c.fill = fill; c.apply = apply;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.h = h; c.w = w; c.B_M = B_M;
+    c.coord_mode = coord_mode; c.norm_coords = norm_coords; c.interp = interp; c.pad = pad; c.align = align; c.dtype = dtype;
+    c.stream = (hipStream_t)stream;
+    return km_warp_fwd_call("km_warp2d_fwd_masked", c);
 }
 
 // Replaces autograd of the above: aten::grid_sampler_2d_backward + the reverse of the grid chain.
@@ -1167,45 +1156,42 @@ int km_warp2d_bwd_ws(const void* gout, const void* src, const void* mat, void* g
                      int W, int h, int w, int B_M, int coord_mode, int norm_coords, int interp, int pad, int align,
                      const void* fill, int dtype, void* workspace, long long workspace_bytes, void* stream) {
     if (B == 0 || C == 0) return 0;
-    if (km_warp_validate("km_warp2d_bwd", src, mat, B, C, H, W, h, w, B_M, coord_mode, interp, pad, fill, dtype)) return -1;
+    KmWarpCall c;
+    c.gout = gout; c.src = src; c.mat = mat; c.gsrc = gsrc; c.gmat = gmat; c.fill = fill;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.h = h; c.w = w; c.B_M = B_M;
+    c.coord_mode = coord_mode; c.norm_coords = norm_coords; c.interp = interp; c.pad = pad; c.align = align; c.dtype = dtype;
+    c.stream = (hipStream_t)stream;
+    if (km_warp_validate("km_warp2d_bwd", c)) return -1;
     KM_REQUIRE(gout, "km_warp2d_bwd: null gout");
     if (!gsrc && !gmat) return 0;
-    hipStream_t s = (hipStream_t)stream;
     // bilinear + zeros/fill: grad_src by the tile-owner scatter, the matrix gradient by its own forward-shaped kernel
-    const bool gm_fast = gmat && km_warp_gm_supported(interp, pad, dtype, H, W, h, w);
+    const bool gm_fast = gmat && km_warp_gm_supported(c);
     // border / reflection padding: the tile-owner kernel of the one-read backward is the only scatter without global atomics for these
     // modes, so it also serves a call that wants the image gradient alone (gmat == nullptr: nothing is committed)
-    if (gsrc && workspace && (pad == KM_PAD_BORDER || pad == KM_PAD_REFLECTION) && km_warp_bwd_tiled_dims_ok(h, w) && !km_config().warp_bwd_generic &&
-        km_warp_bwd_fused_supported(interp, pad, dtype, C, H, W, h, w) &&
-        (unsigned long long)workspace_bytes >= (unsigned long long)km_warp_bwd_fused_workspace(B, C, H, W) && ((uintptr_t)workspace & 15) == 0)
-        return km_warp_bwd_fused_run(gout, src, mat, gsrc, gmat, workspace, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, fill, dtype, s);
-    if (km_warp_bwd_tiled_supported(interp, pad, dtype, gsrc)) {
-        if (km_warp_bwd_tiled_dims_ok(h, w)) {
+    if (gsrc && (pad == KM_PAD_BORDER || pad == KM_PAD_REFLECTION) && km_warp_bwd_tiled_dims_ok(c) && !km_config().warp_bwd_generic &&
+        km_bwd_one_read_ok(c, workspace, workspace_bytes))
+        return km_warp_bwd_fused_run(c, workspace);
+    if (km_warp_bwd_tiled_supported(c)) {
+        if (km_warp_bwd_tiled_dims_ok(c)) {
             // both gradients wanted: one persistent launch that reads grad_out once (3e bytes per element instead of 4e)
-            if (gmat && workspace && km_warp_bwd_fused_supported(interp, pad, dtype, C, H, W, h, w) &&
-                (unsigned long long)workspace_bytes >= (unsigned long long)km_warp_bwd_fused_workspace(B, C, H, W) && ((uintptr_t)workspace & 15) == 0)
-                return km_warp_bwd_fused_run(gout, src, mat, gsrc, gmat, workspace, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, fill, dtype, s);
+            if (gmat && km_bwd_one_read_ok(c, workspace, workspace_bytes)) return km_warp_bwd_fused_run(c, workspace);
             // scatter first, matrix gradient second: with the alternating batch traversal (km_traversal_next) the second launch starts on the
             // part of grad_out the first one read last.  (The other order measured 1.868 against 1.845 ms per step - no better than a fixed direction.)
-            const int rc = km_warp_bwd_tiled_run(gout, mat, gsrc, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, dtype, s);
+            const int rc = km_warp_bwd_tiled_run(c);
             if (rc != 0 || !gmat) return rc;
-            if (gm_fast) return km_warp_gm_run(gout, src, mat, gmat, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, fill, dtype, s);
-            gsrc = nullptr;  // matrix gradient by the generic kernel below (W < 2)
-        } else {
-            // planes beyond 2^30 pixels: generic atomic scatter; the caller was told not to zero grad_src (needs_zero_init == 0)
-            const size_t esz = 4;  // fp32 accumulators (fp64 never reaches this branch)
-            const hipError_t e = hipMemsetAsync(gsrc, 0, (size_t)B * C * H * W * esz, s);
-            if (e != hipSuccess) { km_set_error("km_warp2d_bwd: hipMemsetAsync failed: %s", hipGetErrorString(e)); return (int)e; }
+            if (gm_fast) return km_warp_gm_run(c);
+            KmWarpCall m = c;  // matrix gradient by the generic kernel (W < 2)
+            m.gsrc = nullptr;
+            return km_warp_run_any(true, m);
         }
+        // planes beyond 2^30 pixels: generic atomic scatter; the caller was told not to zero grad_src (needs_zero_init == 0)
+        const size_t esz = 4;  // fp32 accumulators (fp64 never reaches this branch)
+        const hipError_t e = hipMemsetAsync(gsrc, 0, (size_t)B * C * H * W * esz, c.stream);
+        if (e != hipSuccess) { km_set_error("km_warp2d_bwd: hipMemsetAsync failed: %s", hipGetErrorString(e)); return (int)e; }
     } else if (!gsrc && gm_fast) {  // matrix gradient only (learned-homography loops: SURVEY.md config 5)
-        return km_warp_gm_run(gout, src, mat, gmat, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, fill, dtype, s);
+        return km_warp_gm_run(c);
     }
-    switch (dtype) {
-        case KM_F32: return km_warp_run<float>(true, src, mat, nullptr, gout, gsrc, gmat, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s);
-        case KM_F64: return km_warp_run<double>(true, src, mat, nullptr, gout, gsrc, gmat, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s);
-        case KM_BF16: return km_warp_run<km_bf16>(true, src, mat, nullptr, gout, gsrc, gmat, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s);
-        default: return km_warp_run<km_f16>(true, src, mat, nullptr, gout, gsrc, gmat, B, C, H, W, h, w, B_M, coord_mode, norm_coords, interp, pad, align, fill, s);
-    }
+    return km_warp_run_any(true, c);
 }
 
 // km_warp2d_bwd_ws without a workspace: the image gradient and the matrix gradient as two launches (each reads grad_out)
@@ -1220,11 +1206,15 @@ int km_warp2d_bwd(const void* gout, const void* src, const void* mat, void* gsrc
 long long km_warp2d_bwd_workspace_bytes(int B, int C, int H, int W, int h, int w, int interp, int pad, int dtype) {
     int dummy = 0;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0) return 0;
+    KmWarpCall c;
+    c.gsrc = &dummy;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.h = h; c.w = w;
+    c.interp = interp; c.pad = pad; c.dtype = dtype;
     const bool in_image_pad = (pad == KM_PAD_BORDER || pad == KM_PAD_REFLECTION);  // (served by the one-read kernel alone)
-    if (km_config().warp_bwd_generic || !km_warp_bwd_tiled_dims_ok(h, w)) return 0;
-    if (!in_image_pad && !km_warp_bwd_tiled_supported(interp, pad, dtype, &dummy)) return 0;
-    if (!km_warp_bwd_fused_supported(interp, pad, dtype, C, H, W, h, w)) return 0;
-    return (long long)km_warp_bwd_fused_workspace(B, C, H, W);
+    if (km_config().warp_bwd_generic || !km_warp_bwd_tiled_dims_ok(c)) return 0;
+    if (!in_image_pad && !km_warp_bwd_tiled_supported(c)) return 0;
+    if (!km_warp_bwd_fused_supported(c)) return 0;
+    return (long long)km_warp_bwd_fused_workspace(c);
 }
 
 // ---- explicit sampling grid: replaces F.grid_sample(input, grid) as called by remap (imgwarp.py:702) and
@@ -1233,16 +1223,15 @@ long long km_warp2d_bwd_workspace_bytes(int B, int C, int H, int W, int h, int w
 int km_grid_sample2d_fwd(const void* src, const void* grid, void* dst, int B, int C, int H, int W, int h, int w, int B_G,
                          int interp, int pad, int align, int dtype, void* stream) {
     if (B == 0 || C == 0 || h == 0 || w == 0) return 0;
-    if (km_warp_validate("km_grid_sample2d_fwd", src, grid, B, C, H, W, h, w, B_G, 0, interp, pad, nullptr, dtype)) return -1;
+    KmWarpCall c;
+    c.src = src; c.mat = grid; c.grid = grid; c.dst = dst;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.h = h; c.w = w; c.B_M = B_G;
+    c.coord_mode = KM_COORD_GRID; c.interp = interp; c.pad = pad; c.align = align; c.dtype = dtype;
+    c.stream = (hipStream_t)stream;
+    if (km_warp_validate("km_grid_sample2d_fwd", c)) return -1;
     KM_REQUIRE(dst, "km_grid_sample2d_fwd: null dst");
     KM_REQUIRE(pad != KM_PAD_FILL, "km_grid_sample2d_fwd: pad must be zeros / border / reflection");
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return km_warp_run<float>(false, src, grid, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_G, KM_COORD_GRID, 0, interp, pad, align, nullptr, s, grid);
-        case KM_F64: return km_warp_run<double>(false, src, grid, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_G, KM_COORD_GRID, 0, interp, pad, align, nullptr, s, grid);
-        case KM_BF16: return km_warp_run<km_bf16>(false, src, grid, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_G, KM_COORD_GRID, 0, interp, pad, align, nullptr, s, grid);
-        default: return km_warp_run<km_f16>(false, src, grid, dst, nullptr, nullptr, nullptr, B, C, H, W, h, w, B_G, KM_COORD_GRID, 0, interp, pad, align, nullptr, s, grid);
-    }
+    return km_warp_run_any(false, c);
 }
 
 // gsrc (B,C,H,W) compute dtype, PRE-ZEROED (fp32 atomics), nullable; ggrid (B,h,w,2) compute dtype, written, nullable
@@ -1250,24 +1239,26 @@ int km_grid_sample2d_fwd(const void* src, const void* grid, void* dst, int B, in
 int km_grid_sample2d_bwd(const void* gout, const void* src, const void* grid, void* gsrc, void* ggrid, int B, int C, int H, int W,
                          int h, int w, int B_G, int interp, int pad, int align, int dtype, void* stream) {
     if (B == 0 || C == 0 || h == 0 || w == 0) return 0;
-    if (km_warp_validate("km_grid_sample2d_bwd", src, grid, B, C, H, W, h, w, B_G, 0, interp, pad, nullptr, dtype)) return -1;
+    KmWarpCall c;
+    c.gout = gout; c.src = src; c.mat = grid; c.grid = grid; c.gsrc = gsrc; c.ggrid = ggrid;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.h = h; c.w = w; c.B_M = B_G;
+    c.coord_mode = KM_COORD_GRID; c.interp = interp; c.pad = pad; c.align = align; c.dtype = dtype;
+    c.stream = (hipStream_t)stream;
+    if (km_warp_validate("km_grid_sample2d_bwd", c)) return -1;
     KM_REQUIRE(gout, "km_grid_sample2d_bwd: null gout");
     KM_REQUIRE(pad != KM_PAD_FILL, "km_grid_sample2d_bwd: pad must be zeros / border / reflection");
     if (!gsrc && !ggrid) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return km_warp_run<float>(true, src, grid, nullptr, gout, gsrc, nullptr, B, C, H, W, h, w, B_G, KM_COORD_GRID, 0, interp, pad, align, nullptr, s, grid, ggrid);
-        case KM_F64: return km_warp_run<double>(true, src, grid, nullptr, gout, gsrc, nullptr, B, C, H, W, h, w, B_G, KM_COORD_GRID, 0, interp, pad, align, nullptr, s, grid, ggrid);
-        case KM_BF16: return km_warp_run<km_bf16>(true, src, grid, nullptr, gout, gsrc, nullptr, B, C, H, W, h, w, B_G, KM_COORD_GRID, 0, interp, pad, align, nullptr, s, grid, ggrid);
-        default: return km_warp_run<km_f16>(true, src, grid, nullptr, gout, gsrc, nullptr, B, C, H, W, h, w, B_G, KM_COORD_GRID, 0, interp, pad, align, nullptr, s, grid, ggrid);
-    }
+    return km_warp_run_any(true, c);
 }
 
 // 1 if km_warp2d_bwd with these modes accumulates with atomics and therefore needs gsrc zeroed by the
 // caller; 0 if it overwrites gsrc completely (owner-computes path).
 int km_warp2d_bwd_needs_zero_init(int interp, int pad, int dtype) {
     int dummy = 0;
-    return km_warp_bwd_tiled_supported(interp, pad, dtype, &dummy) ? 0 : 1;
+    KmWarpCall c;
+    c.gsrc = &dummy;
+    c.interp = interp; c.pad = pad; c.dtype = dtype;
+    return km_warp_bwd_tiled_supported(c) ? 0 : 1;
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "km_warp_args.h"
+#include "km_warp_host.h"
 #include "km_warp_stage.h"
 
 template <typename T>
@@ -367,25 +368,23 @@ static int kmwb_launch(const KmWarpBlurArgs<T>& a, int K, hipStream_t s) {
     return a.g.C == 3 ? kmwb_launch_nc<T, CM, 3>(a, K, s) : kmwb_launch_nc<T, CM, 1>(a, K, s);
 }
 template <typename T>
-static int kmwb_run(const void* src, const void* mat, const void* kx, const void* ky, void* dst, int B, int C, int H, int W, int h, int w, int B_M, int Bk,
-                    int coord_mode, int norm_coords, int align, int K, int border, hipStream_t s) {
+static int kmwb_run(const KmWarpCall& c, const void* kx, const void* ky, int Bk, int K, int border) {
     KmWarpBlurArgs<T> a;
-    a.src = (const T*)src; a.mat = (const float*)mat; a.kx = (const float*)kx; a.ky = (const float*)ky; a.dst = (T*)dst;
-    km_geom_init(a.g, B, C, H, W, h, w, B_M, coord_mode, norm_coords, KM_INTERP_BILINEAR, KM_PAD_ZEROS, align);
+    a.src = (const T*)c.src; a.mat = (const float*)c.mat; a.kx = (const float*)kx; a.ky = (const float*)ky; a.dst = (T*)c.dst;
+    km_geom_init(a.g, c);
     a.Bk = Bk; a.border = border;
-    a.tiles_x = (uint32_t)((w + 63) / 64);
-    a.tiles_y = (uint32_t)((h + 31) / 32);
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B;
+    a.tiles_x = (uint32_t)((c.w + 63) / 64);
+    a.tiles_y = (uint32_t)((c.h + 31) / 32);
+    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)c.B;
     KM_REQUIRE(nb < (1ull << 31), "km_warp2d_blur_fwd: grid too large");
     if (nb == 0) return 0;
     a.nblocks = (uint32_t)nb;
-    a.reverse = km_traversal_next(s);
-    a.stream_out = km_stream_stores((uint64_t)B * C * h * w * sizeof(T));
-    switch (coord_mode) {
-        case KM_COORD_PERSPECTIVE: return kmwb_launch<T, KM_COORD_PERSPECTIVE>(a, K, s);
-        case KM_COORD_AFFINE: return kmwb_launch<T, KM_COORD_AFFINE>(a, K, s);
-        default: return kmwb_launch<T, KM_COORD_HOMOGRAPHY>(a, K, s);
-    }
+    a.reverse = km_traversal_next(c.stream);
+    a.stream_out = km_stream_stores((uint64_t)c.B * c.C * c.h * c.w * sizeof(T));
+    // (the entry point does not check coord_mode: a code that is neither perspective nor affine runs as a homography, as it always has)
+    const int cm = (c.coord_mode == KM_COORD_PERSPECTIVE || c.coord_mode == KM_COORD_AFFINE) ? c.coord_mode : KM_COORD_HOMOGRAPHY;
+    return km_dispatch_coord<KM_COORD_PERSPECTIVE, KM_COORD_AFFINE, KM_COORD_HOMOGRAPHY>(
+        cm, -1, [&](auto t) { return kmwb_launch<T, decltype(t)::value>(a, K, c.stream); });
 }
 
 extern "C" {
@@ -401,15 +400,17 @@ int km_warp2d_blur_supported(int C, int H, int W, int h, int w, int interp, int 
 
 int km_warp2d_blur_fwd(const void* src, const void* mat, const void* kx, const void* ky, void* dst, int B, int C, int H, int W, int h, int w, int B_M, int Bk,
                        int coord_mode, int norm_coords, int align_corners, int K, int border, int dtype, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
     KM_REQUIRE(km_warp2d_blur_supported(C, H, W, h, w, KM_INTERP_BILINEAR, KM_PAD_ZEROS, K, border, dtype), "km_warp2d_blur_fwd: unsupported modes (km_warp2d_blur_supported)");
     KM_REQUIRE(B_M == 1 || B_M == B, "km_warp2d_blur_fwd: B_M must be 1 or B");
     KM_REQUIRE(Bk >= 1, "km_warp2d_blur_fwd: Bk must be >= 1");
-    switch (dtype) {
-        case KM_F32: return kmwb_run<float>(src, mat, kx, ky, dst, B, C, H, W, h, w, B_M, Bk, coord_mode, norm_coords, align_corners, K, border, s);
-        case KM_BF16: return kmwb_run<km_bf16>(src, mat, kx, ky, dst, B, C, H, W, h, w, B_M, Bk, coord_mode, norm_coords, align_corners, K, border, s);
-        default: return kmwb_run<km_f16>(src, mat, kx, ky, dst, B, C, H, W, h, w, B_M, Bk, coord_mode, norm_coords, align_corners, K, border, s);
-    }
+    KmWarpCall c;
+    c.src = src; c.mat = mat; c.dst = dst;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.h = h; c.w = w; c.B_M = B_M;
+    c.coord_mode = coord_mode; c.norm_coords = norm_coords; c.interp = KM_INTERP_BILINEAR; c.pad = KM_PAD_ZEROS; c.align = align_corners;
+    // (km_warp2d_blur_supported turns away f64 alone: any other code that is neither f32 nor bf16 runs as f16, as it always has)
+    c.dtype = (dtype == KM_F32 || dtype == KM_BF16) ? dtype : KM_F16;
+    c.stream = (hipStream_t)stream;
+    return km_dispatch_dtype<float, km_bf16, km_f16>(c.dtype, -1, [&](auto t) { return kmwb_run<KM_TAG_T(t)>(c, kx, ky, Bk, K, border); });
 }
 
 }  // extern "C"

@@ -53,6 +53,7 @@
 #include <atomic>
 
 #include "km_warp_gm_rows.h"
+#include "km_warp_host.h"
 #include "km_warp_tile.h"
 
 // KMO_PROFILE (variant libraries only, profiles/time_bwd_phases.py): every wave sums the shader cycles (s_memtime) it spends in each phase
@@ -1430,69 +1431,61 @@ static int kmo_run_groups(KmWarpFusedArgs<T>& a, int B, uint32_t c0, uint32_t ng
         a.general_tiles = (uint32_t)(per < 1 ? 1 : (per > 64 ? 64 : per));
         a.general_grid = workers_max;
     }
-    switch (coord_mode) {
-        case KM_COORD_PERSPECTIVE: return kmo_launch<T, KM_COORD_PERSPECTIVE>(a, s);
-        case KM_COORD_AFFINE: return kmo_launch<T, KM_COORD_AFFINE>(a, s);
-        default: return kmo_launch<T, KM_COORD_HOMOGRAPHY>(a, s);
-    }
+    return km_dispatch_coord<KM_COORD_PERSPECTIVE, KM_COORD_AFFINE, KM_COORD_HOMOGRAPHY>(
+        coord_mode, -1, [&](auto cm) { return kmo_launch<T, decltype(cm)::value>(a, s); });
 }
 
 template <typename T>
-static int kmo_run(const void* gout, const void* src, const void* mat, void* gsrc, double* gmat, void* ws, int B, int C, int H, int W, int h, int w, int B_M,
-                   int coord_mode, int norm_coords, int pad, int align, const void* fill, hipStream_t s) {
+static int kmo_run(const KmWarpCall& c, void* ws) {
     KmWarpFusedArgs<T> a;
-    a.gout = (const T*)gout; a.src = (const T*)src; a.mat = (const float*)mat; a.gsrc = (float*)gsrc; a.gmat = gmat; a.fill = (const float*)fill;
+    a.gout = (const T*)c.gout; a.src = (const T*)c.src; a.mat = (const float*)c.mat; a.gsrc = (float*)c.gsrc; a.gmat = c.gmat; a.fill = (const float*)c.fill;
     a.ws = (int*)ws;
-    KmWarpGeom<float>& g = a.g;
-    km_geom_init(g, B, C, H, W, h, w, B_M, coord_mode, norm_coords, KM_INTERP_BILINEAR, pad, align);
-    a.tiles_x = (uint32_t)((W + KMT_TW - 1) / KMT_TW);
-    a.tiles_y = (uint32_t)((H + KMO_TH - 1) / KMO_TH);
+    km_geom_init(a.g, c);
+    a.tiles_x = (uint32_t)((c.W + KMT_TW - 1) / KMT_TW);
+    a.tiles_y = (uint32_t)((c.H + KMO_TH - 1) / KMO_TH);
     // C = 3 a3 + r1: the groups of three through the RGB instantiation, the rest one channel at a time through the grey one
-    const uint32_t a3 = (uint32_t)C / 3u, r1 = (uint32_t)C % 3u;
+    const uint32_t a3 = (uint32_t)c.C / 3u, r1 = (uint32_t)c.C % 3u;
     const uint64_t per_image = (uint64_t)a.tiles_x * a.tiles_y;
-    KM_REQUIRE(per_image * (uint64_t)B * (a3 > r1 ? a3 : r1) < (1ull << 26) && (uint64_t)B * (uint64_t)C < (1ull << 31) && a.tiles_x < 65536u && a.tiles_y < 65536u,
+    KM_REQUIRE(per_image * (uint64_t)c.B * (a3 > r1 ? a3 : r1) < (1ull << 26) && (uint64_t)c.B * (uint64_t)c.C < (1ull << 31) && a.tiles_x < 65536u && a.tiles_y < 65536u,
                "km_warp2d_bwd: grid too large");
-    if (per_image * (uint64_t)B == 0 || C == 0)  // (nothing to add: the accumulators are still this path's to zero; gmat == nullptr: image gradient only)
-        return (gmat && B_M > 0) ? (int)hipMemsetAsync(gmat, 0, (size_t)B_M * 9 * sizeof(double), s) : 0;
-    a.reverse = km_traversal_next(s);
-    a.stream_out = km_stream_stores((uint64_t)B * C * H * W * sizeof(float));
+    if (per_image * (uint64_t)c.B == 0 || c.C == 0)  // (nothing to add: the accumulators are still this path's to zero; gmat == nullptr: image gradient only)
+        return (c.gmat && c.B_M > 0) ? (int)hipMemsetAsync(c.gmat, 0, (size_t)c.B_M * 9 * sizeof(double), c.stream) : 0;
+    a.reverse = km_traversal_next(c.stream);
+    a.stream_out = km_stream_stores((uint64_t)c.B * c.C * c.H * c.W * sizeof(float));
     int rc = 0;
-    if (a3) rc = kmo_run_groups(a, B, 0u, a3, 3u, true, coord_mode, s);
-    if (rc == 0 && r1) rc = kmo_run_groups(a, B, 3u * a3, r1, 1u, a3 == 0, coord_mode, s);
+    if (a3) rc = kmo_run_groups(a, c.B, 0u, a3, 3u, true, c.coord_mode, c.stream);
+    if (rc == 0 && r1) rc = kmo_run_groups(a, c.B, 3u * a3, r1, 1u, a3 == 0, c.coord_mode, c.stream);
     return rc;
 }
 
 // 1 if the one-read kernel computes both gradients for these modes (bilinear, every padding mode - border / reflection with fp32 storage -,
 // fp32 compute; any channel count - fill
 // values are per channel of an RGB / grey image, so `fill` keeps C in {1, 3})
-int km_warp_bwd_fused_supported(int interp, int pad, int dtype, int C, int H, int W, int h, int w) {
+int km_warp_bwd_fused_supported(const KmWarpCall& c) {
     if (!km_config().warp_bwd_fused) return 0;
-    if (!(interp == KM_INTERP_BILINEAR && dtype != KM_F64)) return 0;
-    if ((pad == KM_PAD_BORDER || pad == KM_PAD_REFLECTION) && dtype != KM_F32) return 0;  // (these two: fp32 storage)
-    if (C < 1 || (pad == KM_PAD_FILL && !(C == 1 || C == 3))) return 0;
-    // 32-bit byte offsets inside a plane
-    return ((uint64_t)H * W * 4 < (1ull << 32) && (uint64_t)h * w * 4 < (1ull << 32)) ? 1 : 0;
+    if (!(c.interp == KM_INTERP_BILINEAR && c.dtype != KM_F64)) return 0;
+    if ((c.pad == KM_PAD_BORDER || c.pad == KM_PAD_REFLECTION) && c.dtype != KM_F32) return 0;  // (these two: fp32 storage)
+    if (c.C < 1 || (c.pad == KM_PAD_FILL && !(c.C == 1 || c.C == 3))) return 0;
+    return km_warp_planes_fit_u32(c) ? 1 : 0;
 }
 
 // bytes of workspace the one-read backward needs for these sizes: one KMO_BOX_INTS * 4 = 80-byte record per 64 x 64 tile of the source and
 // channel group of the larger of its (at most two) launch sequences
-size_t km_warp_bwd_fused_workspace(int B, int C, int H, int W) {
-    const uint64_t a3 = (uint64_t)C / 3u, r1 = (uint64_t)C % 3u;
-    const uint64_t ntiles = (uint64_t)((W + KMT_TW - 1) / KMT_TW) * (uint64_t)((H + KMO_TH - 1) / KMO_TH) * (uint64_t)B * (a3 > r1 ? a3 : r1);
+size_t km_warp_bwd_fused_workspace(const KmWarpCall& c) {
+    const uint64_t a3 = (uint64_t)c.C / 3u, r1 = (uint64_t)c.C % 3u;
+    const uint64_t ntiles = (uint64_t)((c.W + KMT_TW - 1) / KMT_TW) * (uint64_t)((c.H + KMO_TH - 1) / KMO_TH) * (uint64_t)c.B * (a3 > r1 ? a3 : r1);
     return (size_t)(ntiles * KMO_BOX_INTS * sizeof(int));
 }
 
-int km_warp_bwd_fused_run(const void* gout, const void* src, const void* mat, void* gsrc, double* gmat, void* ws, int B, int C, int H, int W, int h, int w,
-                          int B_M, int coord_mode, int norm_coords, int pad, int align, const void* fill, int dtype, hipStream_t s) {
-    switch (dtype) {
-        case KM_F32: return kmo_run<float>(gout, src, mat, gsrc, gmat, ws, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, fill, s);
-#ifndef KMO_DEV_F32_ONLY  // (development builds: one storage type compiles in a third of the time)
-        case KM_BF16: return kmo_run<km_bf16>(gout, src, mat, gsrc, gmat, ws, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, fill, s);
-        default: return kmo_run<km_f16>(gout, src, mat, gsrc, gmat, ws, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, fill, s);
-#else
-        default: return -1;
+#ifndef KMO_DEV_F32_ONLY
+#define KMO_STORAGE_TYPES float, km_bf16, km_f16
+#else  // (development builds: one storage type compiles in a third of the time)
+#define KMO_STORAGE_TYPES float
 #endif
-    }
+
+// the call is one km_warp_bwd_fused_supported() takes
+int km_warp_bwd_fused_run(const KmWarpCall& c, void* ws) {
+    return km_dispatch_dtype<KMO_STORAGE_TYPES>(c.dtype, -1, [&](auto t) { return kmo_run<KM_TAG_T(t)>(c, ws); });
 }
 
 #ifdef KMO_PROFILE

@@ -33,6 +33,7 @@
 // the 12 quantise+atomic pairs), not HBM bound: see DESIGN.md for the counters.
 #include <stdlib.h>
 
+#include "km_warp_host.h"
 #include "km_warp_tile.h"
 
 #define KMT_NT 512          // threads per workgroup
@@ -456,46 +457,39 @@ static int kmt_launch(const KmWarpTiledArgs<T>& a, hipStream_t s) {
 }
 
 template <typename T>
-static int kmt_run(const void* gout, const void* mat, void* gsrc, int B, int C, int H, int W, int h, int w, int B_M, int coord_mode, int norm_coords, int pad,
-                   int align, hipStream_t s) {
+static int kmt_run(const KmWarpCall& c) {
     KmWarpTiledArgs<T> a;
-    a.gout = (const T*)gout; a.mat = (const float*)mat; a.gsrc = (float*)gsrc;
-    KmWarpGeom<float>& g = a.g;
-    km_geom_init(g, B, C, H, W, h, w, B_M, coord_mode, norm_coords, KM_INTERP_BILINEAR, pad, align);
-    a.tiles_x = (uint32_t)((W + KMT_TW - 1) / KMT_TW);
-    a.tiles_y = (uint32_t)((H + KMT_TH - 1) / KMT_TH);
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B;
+    a.gout = (const T*)c.gout; a.mat = (const float*)c.mat; a.gsrc = (float*)c.gsrc;
+    km_geom_init(a.g, c);
+    a.tiles_x = (uint32_t)((c.W + KMT_TW - 1) / KMT_TW);
+    a.tiles_y = (uint32_t)((c.H + KMT_TH - 1) / KMT_TH);
+    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)c.B;
     KM_REQUIRE(nb < (1ull << 31), "km_warp2d_bwd: grid too large");
     a.nblocks = (uint32_t)nb;
     if (nb == 0) return 0;
-    a.reverse = km_traversal_next(s);
-    a.stream_out = km_stream_stores((uint64_t)B * C * H * W * sizeof(float));
-    switch (coord_mode) {
-        case KM_COORD_PERSPECTIVE: return kmt_launch<T, KM_COORD_PERSPECTIVE>(a, s);
-        case KM_COORD_AFFINE: return kmt_launch<T, KM_COORD_AFFINE>(a, s);
-        default: return kmt_launch<T, KM_COORD_HOMOGRAPHY>(a, s);
-    }
+    a.reverse = km_traversal_next(c.stream);
+    a.stream_out = km_stream_stores((uint64_t)c.B * c.C * c.H * c.W * sizeof(float));
+    return km_dispatch_coord<KM_COORD_PERSPECTIVE, KM_COORD_AFFINE, KM_COORD_HOMOGRAPHY>(
+        c.coord_mode, -1, [&](auto cm) { return kmt_launch<T, decltype(cm)::value>(a, c.stream); });
 }
 
 // 1 if the tile-owner kernel computes grad_src for these modes (bilinear, zeros/fill padding, fp32 compute)
-int km_warp_bwd_tiled_supported(int interp, int pad, int dtype, const void* gsrc) {
+int km_warp_bwd_tiled_supported(const KmWarpCall& c) {
     if (km_config().warp_bwd_generic) return 0;  // KM_WARP_BWD_ALGO=generic forces the atomic scatter kernel
-    return (interp == KM_INTERP_BILINEAR && (pad == KM_PAD_ZEROS || pad == KM_PAD_FILL) && dtype != KM_F64 && gsrc != nullptr) ? 1 : 0;
+    return (c.interp == KM_INTERP_BILINEAR && (c.pad == KM_PAD_ZEROS || c.pad == KM_PAD_FILL) && c.dtype != KM_F64 && c.gsrc != nullptr) ? 1 : 0;
 }
 
 // 32-bit byte offsets inside a grad_out plane (the caller falls back to the generic kernel otherwise)
-int km_warp_bwd_tiled_dims_ok(int h, int w) { return ((uint64_t)h * (uint64_t)w * 4 < (1ull << 32)) ? 1 : 0; }
+int km_warp_bwd_tiled_dims_ok(const KmWarpCall& c) { return ((uint64_t)c.h * (uint64_t)c.w * 4 < (1ull << 32)) ? 1 : 0; }
 
-// grad_src (pad zeros / fill does not change it)
-int km_warp_bwd_tiled_run(const void* gout, const void* mat, void* gsrc, int B, int C, int H, int W, int h, int w, int B_M, int coord_mode, int norm_coords,
-                          int pad, int align, int dtype, hipStream_t s) {
-    switch (dtype) {
-        case KM_F32: return kmt_run<float>(gout, mat, gsrc, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, s);
-#ifndef KMT_DEV_F32_ONLY  // (development builds: one storage type compiles in a third of the time)
-        case KM_BF16: return kmt_run<km_bf16>(gout, mat, gsrc, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, s);
-        default: return kmt_run<km_f16>(gout, mat, gsrc, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, s);
-#else
-        default: return -1;
+#ifndef KMT_DEV_F32_ONLY
+#define KMT_STORAGE_TYPES float, km_bf16, km_f16
+#else  // (development builds: one storage type compiles in a third of the time)
+#define KMT_STORAGE_TYPES float
 #endif
-    }
+
+// grad_src (pad zeros / fill does not change it); the call is one km_warp_bwd_tiled_supported() takes
+int km_warp_bwd_tiled_run(const KmWarpCall& c) {
+    return km_dispatch_dtype<KMT_STORAGE_TYPES>(c.dtype, -1, [&](auto t) { return kmt_run<KM_TAG_T(t)>(c); });
 }
+

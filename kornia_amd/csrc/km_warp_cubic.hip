@@ -4,6 +4,7 @@
 // vectorizer's v_pk_mul_f32 / v_pk_add_f32 pairs cost more issue time than the scalar ops they replace once the v_mov
 // shuffles that feed them are counted (profiles/r02_valu_rates.txt: v_pk_* 2.1 ns for two results, v_mul / v_add 1.2 ns each).
 #include "km_warp_args.h"
+#include "km_warp_host.h"
 #include "km_warp_stage.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -229,20 +230,13 @@ static bool km_warp_fwd_cubic_try(const KmWarpArgs<T>& a, hipStream_t s) {
     return false;
 }
 
-
-int km_warp_fwd_cubic_try_any(int dtype, int coord_mode, const void* args, hipStream_t s) {
-#define KMQ_CM(T)                                                                                                              \
-    switch (coord_mode) {                                                                                                      \
-        case KM_COORD_PERSPECTIVE: return km_warp_fwd_cubic_try<T, KM_COORD_PERSPECTIVE>(*(const KmWarpArgs<T>*)args, s) ? 1 : 0; \
-        case KM_COORD_AFFINE: return km_warp_fwd_cubic_try<T, KM_COORD_AFFINE>(*(const KmWarpArgs<T>*)args, s) ? 1 : 0;           \
-        case KM_COORD_HOMOGRAPHY: return km_warp_fwd_cubic_try<T, KM_COORD_HOMOGRAPHY>(*(const KmWarpArgs<T>*)args, s) ? 1 : 0;   \
-        default: return 0;                                                                                                     \
-    }
-    switch (dtype) {
-        case KM_F32: KMQ_CM(float)
-        case KM_BF16: KMQ_CM(km_bf16)
-        case KM_F16: KMQ_CM(km_f16)
-        default: return 0;  // fp64 computes in double: the generic kernel
-    }
-#undef KMQ_CM
+template <typename T>
+static int kmq_try_any(const KmWarpArgs<T>& a, int coord_mode, hipStream_t s) {
+    return km_dispatch_coord<KM_COORD_PERSPECTIVE, KM_COORD_AFFINE, KM_COORD_HOMOGRAPHY>(
+        coord_mode, 0, [&](auto cm) { return km_warp_fwd_cubic_try<T, decltype(cm)::value>(a, s) ? 1 : 0; });
 }
+// (the storage types with fp32 compute; fp64 computes in double: the generic kernel)
+int km_warp_fwd_cubic_try_any(const KmWarpArgs<float>& a, int coord_mode, hipStream_t s) { return kmq_try_any(a, coord_mode, s); }
+int km_warp_fwd_cubic_try_any(const KmWarpArgs<km_bf16>& a, int coord_mode, hipStream_t s) { return kmq_try_any(a, coord_mode, s); }
+int km_warp_fwd_cubic_try_any(const KmWarpArgs<km_f16>& a, int coord_mode, hipStream_t s) { return kmq_try_any(a, coord_mode, s); }
+

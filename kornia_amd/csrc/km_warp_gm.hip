@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "km_warp_gm_rows.h"
+#include "km_warp_host.h"
 
 template <typename T, int CM, int NC, int ALIGN>  // NC = 3 / 1: RGB / grey unrolled ; NC = 0: runtime channel loop
 __global__ __launch_bounds__(256) void km_warp_gm_kernel(const KmWarpGmArgs<T> a) {
@@ -209,47 +210,35 @@ static int kmg_launch(const KmWarpGmArgs<T>& a, hipStream_t s) {
     return km_check_launch("km_warp2d_bwd(matrix gradient)");
 }
 
-// the box form (km_warp_gm_box.hip): launches and returns 1 when it takes the case, 0 otherwise
-int km_warp_gm_box_try(const void* args, int coord_mode, hipStream_t s);
-
 template <typename T>
-static int kmg_run(const void* gout, const void* src, const void* mat, double* gmat, int B, int C, int H, int W, int h, int w, int B_M,
-                   int coord_mode, int norm_coords, int pad, int align, const void* fill, hipStream_t s) {
+static int kmg_run(const KmWarpCall& c) {
     KmWarpGmArgs<T> a;
-    a.src = (const T*)src; a.gout = (const T*)gout; a.mat = (const float*)mat; a.gmat = gmat; a.fill = (const float*)fill;
-    KmWarpGeom<float>& g = a.g;
-    km_geom_init(g, B, C, H, W, h, w, B_M, coord_mode, norm_coords, KM_INTERP_BILINEAR, pad, align);
-    a.tiles_x = (uint32_t)((w + KMG_TILE_W - 1) / KMG_TILE_W);
-    a.tiles_y = (uint32_t)((h + KMG_TILE_H - 1) / KMG_TILE_H);
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B;
+    a.src = (const T*)c.src; a.gout = (const T*)c.gout; a.mat = (const float*)c.mat; a.gmat = c.gmat; a.fill = (const float*)c.fill;
+    km_geom_init(a.g, c);
+    a.tiles_x = (uint32_t)((c.w + KMG_TILE_W - 1) / KMG_TILE_W);
+    a.tiles_y = (uint32_t)((c.h + KMG_TILE_H - 1) / KMG_TILE_H);
+    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)c.B;
     KM_REQUIRE(nb < (1ull << 31), "km_warp2d_bwd: grid too large");
     a.nblocks = (uint32_t)nb;
     if (nb == 0) return 0;
-    a.reverse = km_traversal_next(s);
+    a.reverse = km_traversal_next(c.stream);
     if constexpr (sizeof(T) == 4) {  // fp32 storage, zeros padding, RGB / grey: the box form unless KM_WARP_GM_ALGO says otherwise
-        if (km_config().warp_gm_algo == 0 && km_warp_gm_box_try(&a, coord_mode, s)) return km_check_launch("km_warp2d_bwd(matrix gradient, box)");
+        if (km_config().warp_gm_algo == 0 && km_warp_gm_box_try(a, c.coord_mode, c.stream)) return km_check_launch("km_warp2d_bwd(matrix gradient, box)");
     }
-    switch (coord_mode) {
-        case KM_COORD_PERSPECTIVE: return kmg_launch<T, KM_COORD_PERSPECTIVE>(a, s);
-        case KM_COORD_AFFINE: return kmg_launch<T, KM_COORD_AFFINE>(a, s);
-        default: return kmg_launch<T, KM_COORD_HOMOGRAPHY>(a, s);
-    }
+    return km_dispatch_coord<KM_COORD_PERSPECTIVE, KM_COORD_AFFINE, KM_COORD_HOMOGRAPHY>(
+        c.coord_mode, -1, [&](auto cm) { return kmg_launch<T, decltype(cm)::value>(a, c.stream); });
 }
 
 // 1 if this kernel computes the matrix gradient for these modes (bilinear, zeros / fill padding, fp32 compute)
-int km_warp_gm_supported(int interp, int pad, int dtype, int H, int W, int h, int w) {
+int km_warp_gm_supported(const KmWarpCall& c) {
     if (km_config().warp_gm_algo == 1) return 0;  // KM_WARP_GM_ALGO=generic: the atomic scatter kernel computes it (A/B timing)
-    if (!(interp == KM_INTERP_BILINEAR && (pad == KM_PAD_ZEROS || pad == KM_PAD_FILL) && dtype != KM_F64)) return 0;
-    if (W < 2) return 0;  // the pair loads need two columns
-    // 32-bit byte offsets inside a plane
-    return ((uint64_t)H * W * 4 < (1ull << 32) && (uint64_t)h * w * 4 < (1ull << 32)) ? 1 : 0;
+    if (!(c.interp == KM_INTERP_BILINEAR && (c.pad == KM_PAD_ZEROS || c.pad == KM_PAD_FILL) && c.dtype != KM_F64)) return 0;
+    if (c.W < 2) return 0;  // the pair loads need two columns
+    return km_warp_planes_fit_u32(c) ? 1 : 0;
 }
 
-int km_warp_gm_run(const void* gout, const void* src, const void* mat, double* gmat, int B, int C, int H, int W, int h, int w, int B_M,
-                   int coord_mode, int norm_coords, int pad, int align, const void* fill, int dtype, hipStream_t s) {
-    switch (dtype) {
-        case KM_F32: return kmg_run<float>(gout, src, mat, gmat, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, fill, s);
-        case KM_BF16: return kmg_run<km_bf16>(gout, src, mat, gmat, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, fill, s);
-        default: return kmg_run<km_f16>(gout, src, mat, gmat, B, C, H, W, h, w, B_M, coord_mode, norm_coords, pad, align, fill, s);
-    }
+// the call is one km_warp_gm_supported() takes
+int km_warp_gm_run(const KmWarpCall& c) {
+    return km_dispatch_dtype<float, km_bf16, km_f16>(c.dtype, -1, [&](auto t) { return kmg_run<KM_TAG_T(t)>(c); });
 }
+

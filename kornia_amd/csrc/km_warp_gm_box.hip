@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "km_warp_gm_rows.h"
+#include "km_warp_host.h"
 
 #define KMGB_PITCH 80  // floats per staged source row of the box
 #define KMGB_ROWS 40   // staged source rows
@@ -161,9 +162,9 @@ static void kmgb_launch_nc(const KmWarpGmArgs<float>& a, hipStream_t s) {
 }
 
 // Launches the box form and returns 1 when it takes the case (fp32 storage, zeros padding, C in {1, 3}, 16-byte rows), 0 otherwise
-// (km_warp_gm.hip then runs the gather kernel).  `args`: a KmWarpGmArgs<float> with the geometry filled in.
-int km_warp_gm_box_try(const void* args, int coord_mode, hipStream_t s) {
-    KmWarpGmArgs<float> a = *reinterpret_cast<const KmWarpGmArgs<float>*>(args);
+// (km_warp_gm.hip then runs the gather kernel).  `a0`: the geometry filled in.
+int km_warp_gm_box_try(const KmWarpGmArgs<float>& a0, int coord_mode, hipStream_t s) {
+    KmWarpGmArgs<float> a = a0;
     const KmWarpGeom<float>& g = a.g;
     if (!(g.C == 3 || g.C == 1) || g.pad != KM_PAD_ZEROS || (g.W & 3) != 0 || ((uintptr_t)a.src & 15) != 0 || g.W < 4) return 0;
     if (!((uint64_t)g.H * g.W * 4 < (1ull << 32) && (uint64_t)g.h * g.w * 4 < (1ull << 32) && g.W < (1 << 23) && g.H < (1 << 23))) return 0;
@@ -172,10 +173,9 @@ int km_warp_gm_box_try(const void* args, int coord_mode, hipStream_t s) {
     const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)g.B;
     if (nb == 0 || nb >= (1ull << 31)) return 0;
     a.nblocks = (uint32_t)nb;
-    switch (coord_mode) {
-        case KM_COORD_PERSPECTIVE: g.C == 3 ? kmgb_launch_nc<KM_COORD_PERSPECTIVE, 3>(a, s) : kmgb_launch_nc<KM_COORD_PERSPECTIVE, 1>(a, s); break;
-        case KM_COORD_AFFINE: g.C == 3 ? kmgb_launch_nc<KM_COORD_AFFINE, 3>(a, s) : kmgb_launch_nc<KM_COORD_AFFINE, 1>(a, s); break;
-        default: g.C == 3 ? kmgb_launch_nc<KM_COORD_HOMOGRAPHY, 3>(a, s) : kmgb_launch_nc<KM_COORD_HOMOGRAPHY, 1>(a, s); break;
-    }
-    return 1;
+    return km_dispatch_coord<KM_COORD_PERSPECTIVE, KM_COORD_AFFINE, KM_COORD_HOMOGRAPHY>(coord_mode, 0, [&](auto cm) {
+        constexpr int CM = decltype(cm)::value;
+        g.C == 3 ? kmgb_launch_nc<CM, 3>(a, s) : kmgb_launch_nc<CM, 1>(a, s);
+        return 1;
+    });
 }

@@ -22,7 +22,7 @@
 // walks KML_ROWS rows two at a time with all loads of the pair in flight before the first use when every lane samples inside
 // the image (RGB / grey unrolled); per-thread fp32 partial sums over <= KML_ROWS * C terms, fp64 wave / block reduction,
 // 11 fp64 atomics per block.
-#include "km_sampler.h"
+#include "km_warp_host.h"
 
 // output rows per thread; a wave instruction covers a KML_PATCH_W x (64 / KML_PATCH_W) patch of the output, which keeps the
 // gathered taps compact under rotation (measured for the same access pattern in km_warp_gm.hip)
@@ -228,26 +228,23 @@ static void kml_launch(const KmWarpLossArgs<T>& a, hipStream_t s) {
         hipLaunchKernelGGL((km_warp_loss_kernel<T, CM, 0>), dim3(a.nblocks), dim3(256), 0, s, a);
 }
 
+// c.src under c.mat against the target `dst` (read, not written: it stays beside the record)
 template <typename T>
-static int kml_run(const void* src, const void* dst, const void* mat, double* acc, int B, int C, int H, int W, int h, int w, int B_M,
-                   int coord_mode, int norm_coords, int align, int loss_kind, double threshold, hipStream_t s) {
+static int kml_run(const KmWarpCall& c, const void* dst, double* acc, int loss_kind, double threshold) {
     KmWarpLossArgs<T> a;
-    a.src = (const T*)src; a.dst = (const T*)dst; a.mat = (const float*)mat; a.acc = acc;
+    a.src = (const T*)c.src; a.dst = (const T*)dst; a.mat = (const float*)c.mat; a.acc = acc;
     a.threshold = (float)threshold; a.loss_kind = loss_kind;
-    KmWarpGeom<float>& g = a.g;
-    km_geom_init(g, B, C, H, W, h, w, B_M, coord_mode, norm_coords, KM_INTERP_BILINEAR, KM_PAD_ZEROS, align);
-    a.tiles_x = (uint32_t)((w + KML_TILE_W - 1) / KML_TILE_W);
-    a.tiles_y = (uint32_t)((h + KML_TILE_H - 1) / KML_TILE_H);
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B;
+    km_geom_init(a.g, c);
+    a.tiles_x = (uint32_t)((c.w + KML_TILE_W - 1) / KML_TILE_W);
+    a.tiles_y = (uint32_t)((c.h + KML_TILE_H - 1) / KML_TILE_H);
+    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)c.B;
     KM_REQUIRE(nb < (1ull << 31), "km_warp_masked_loss: grid too large");
     a.nblocks = (uint32_t)nb;
     if (nb == 0) return 0;
-    switch (coord_mode) {
-        case KM_COORD_PERSPECTIVE: kml_launch<T, KM_COORD_PERSPECTIVE>(a, s); break;
-        case KM_COORD_AFFINE: kml_launch<T, KM_COORD_AFFINE>(a, s); break;
-        default: kml_launch<T, KM_COORD_HOMOGRAPHY>(a, s); break;
-    }
-    return km_check_launch("km_warp_masked_loss");
+    return km_dispatch_coord<KM_COORD_PERSPECTIVE, KM_COORD_AFFINE, KM_COORD_HOMOGRAPHY>(c.coord_mode, -1, [&](auto cm) {
+        kml_launch<T, decltype(cm)::value>(a, c.stream);
+        return km_check_launch("km_warp_masked_loss");
+    });
 }
 
 // ---- what follows the accumulators: the two sums over the batch and the divisions, ONE launch ------------------------------------------
@@ -326,12 +323,12 @@ int km_warp_masked_loss(const void* src, const void* dst, const void* mat, doubl
     KM_REQUIRE((uint64_t)H * W * 4 < (1ull << 32) && (uint64_t)h * w * 4 < (1ull << 32), "km_warp_masked_loss: plane too large for 32-bit offsets");
     if ((uint64_t)B * C * h * w == 0) return 0;
     KM_REQUIRE(src && dst && mat && acc, "km_warp_masked_loss: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case KM_F32: return kml_run<float>(src, dst, mat, acc, B, C, H, W, h, w, B_M, coord_mode, norm_coords, align ? 1 : 0, loss_kind, threshold, s);
-        case KM_BF16: return kml_run<km_bf16>(src, dst, mat, acc, B, C, H, W, h, w, B_M, coord_mode, norm_coords, align ? 1 : 0, loss_kind, threshold, s);
-        default: return kml_run<km_f16>(src, dst, mat, acc, B, C, H, W, h, w, B_M, coord_mode, norm_coords, align ? 1 : 0, loss_kind, threshold, s);
-    }
+    KmWarpCall c;
+    c.src = src; c.mat = mat;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.h = h; c.w = w; c.B_M = B_M;
+    c.coord_mode = coord_mode; c.norm_coords = norm_coords; c.interp = KM_INTERP_BILINEAR; c.pad = KM_PAD_ZEROS; c.align = align ? 1 : 0; c.dtype = dtype;
+    c.stream = (hipStream_t)stream;
+    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kml_run<KM_TAG_T(t)>(c, dst, acc, loss_kind, threshold); });
 }
 
 }  // extern "C"

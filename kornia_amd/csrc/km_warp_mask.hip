@@ -19,6 +19,7 @@
 // pixel for both) or in TWO - the image through km_warp2d_fwd_masked, its kernels untouched, then this kernel on the same matrix and
 // switch; the image is bit-identical to km_warp2d_fwd_masked either way.  Which one runs: KM_PAIR_FUSED_DEFAULT (km_common.h).
 #include "km_warp_args.h"
+#include "km_warp_host.h"
 #include "km_mask.h"
 
 struct KmMaskArgs {
@@ -202,9 +203,6 @@ static void km_warp_mask_dispatch_dt(const KmMaskArgs& a, int dtype, int coord_m
 
 extern "C" {
 
-int km_warp2d_fwd_masked(const void* src, const void* mat, void* dst, const void* apply, int B, int C, int H, int W, int h, int w, int B_M,
-                         int coord_mode, int norm_coords, int interp, int pad, int align, const void* fill, int dtype, void* stream);
-
 // Image + one label mask under the same normalised matrix and per-sample switch (kornia/augmentation/container/augment.py:596-618 with
 // _2d/geometric/base.py:87-130).  src / dst (B,C,H,W) image dtype - both null: the mask alone; mask_src / mask_dst (B,Cm,H,W) in mask_dtype
 // (KM_MASK_*); mat (B,9) fp32 normalised dst->src (coord_mode KM_WARP_AFFINE or KM_WARP_PERSPECTIVE); apply (B) uint8 or null; fill (C) fp32,
@@ -230,15 +228,22 @@ int km_warp2d_pair_fwd(const void* src, void* dst, const void* mask_src, void* m
     // than the second launch costs), perspective ones take the pair kernel
     const int pf = km_config().pair_fused;
     const bool fused = src && C > 0 && Cm > 0 && interp != KM_INTERP_BICUBIC && (pf == 1 || (pf == 2 && coord_mode == KM_COORD_PERSPECTIVE));
+    // the image's warp: same size, one normalised matrix per sample
+    KmWarpCall c;
+    c.src = src; c.mat = mat; c.dst = dst; c.fill = fill; c.apply = apply;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.h = H; c.w = W; c.B_M = B;
+    c.coord_mode = coord_mode; c.norm_coords = 1; c.interp = interp; c.pad = pad; c.align = align; c.dtype = dtype;
+    c.stream = s;
     if (src && C > 0 && !fused) {
-        const int rc = km_warp2d_fwd_masked(src, mat, dst, apply, B, C, H, W, H, W, B, coord_mode, 1, interp, pad, align, fill, dtype, stream);
+        const int rc = km_warp_fwd_call("km_warp2d_fwd_masked", c);
         if (rc) return rc;
     }
     if (Cm == 0) return 0;
     KmMaskArgs a;
     a.src = mask_src; a.dst = mask_dst; a.mat = (const float*)mat; a.apply = (const uint8_t*)apply; a.fill = (const float*)mask_fill;
     a.isrc = src; a.idst = dst; a.ifill = (const float*)fill; a.C = C;
-    km_geom_init(a.g, B, Cm, H, W, H, W, B, coord_mode, 1, interp, pad, align);
+    c.C = Cm;  // the mask's geometry: the image's with the mask's channel count
+    km_geom_init(a.g, c);
     a.groups = 0;
     a.blocks_per_plane = 0;
     switch (mask_dtype) {

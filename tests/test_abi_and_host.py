@@ -58,6 +58,72 @@ def test_bad_arguments_return_error_codes_without_a_gpu():
     assert lib.km_scale_f64(None, None, 0, None, 0, 0, None) == 0  # nothing to do
 
 
+def test_warp_entry_points_host_contract_without_a_gpu():
+    """What the warp entry points decide on the host, before any launch: the argument checks with their messages, the empty
+    calls, and the two predicates the Python layer plans its buffers with (closed forms over every mode code)."""
+    from kornia_amd import _native
+
+    lib = _native.lib()
+    buf = ctypes.create_string_buffer(64)
+
+    def fwd(src=buf, mat=buf, dst=buf, B=1, C=3, H=8, W=8, h=8, w=8, B_M=1, cm=0, interp=1, pad=0, fill=None, dtype=0, fn=lib.km_warp2d_fwd, extra=()):
+        return fn(src, mat, dst, *extra, B, C, H, W, h, w, B_M, cm, 1, interp, pad, 1, fill, dtype, None)
+
+    def rejected(rc, fragment):
+        assert rc < 0 and fragment in lib.km_last_error(), (rc, fragment, lib.km_last_error())
+
+    rejected(fwd(src=None, mat=None, dst=None), b"null pointer")
+    rejected(fwd(B=2, B_M=3), b"matrix batch 3 must be 1 or 2")
+    rejected(fwd(cm=3), b"bad coord_mode 3")
+    rejected(fwd(interp=3), b"bad interp 3")
+    rejected(fwd(pad=4), b"bad pad 4")
+    rejected(fwd(pad=3), b"pad=fill needs fill values")
+    rejected(fwd(dtype=4), b"bad dtype 4")
+    rejected(fwd(H=65536, W=32768), b"image plane exceeds 2^31 elements")
+    rejected(fwd(H=0), b"bad shape")
+    rejected(fwd(dst=None), b"km_warp2d_fwd: null dst")
+    assert fwd(src=None, mat=None, dst=None, B=0) == 0 and fwd(src=None, mat=None, dst=None, h=0) == 0  # empty outputs
+
+    masked = dict(fn=lib.km_warp2d_fwd_masked, extra=(buf,))
+    rejected(fwd(h=4, w=4, **masked), b"needs equal source and destination sizes")
+    rc = fwd(src=None, mat=None, dst=None, fn=lib.km_warp2d_fwd_masked, extra=(None,))
+    assert rc < 0 and lib.km_last_error().startswith(b"km_warp2d_fwd_masked:") and b"null pointer" in lib.km_last_error()
+
+    def bwd_ws(gout=buf, gsrc=buf, gmat=buf, B=1):
+        return lib.km_warp2d_bwd_ws(gout, buf, buf, gsrc, gmat, B, 3, 8, 8, 8, 8, 1, 0, 1, 1, 0, 1, None, 0, None, 0, None)
+
+    rejected(bwd_ws(gout=None), b"km_warp2d_bwd: null gout")
+    assert bwd_ws(gsrc=None, gmat=None) == 0
+    assert lib.km_warp2d_bwd(None, None, None, None, None, 0, 3, 8, 8, 8, 8, 1, 0, 1, 1, 0, 1, None, 0, None) == 0
+
+    rejected(lib.km_grid_sample2d_fwd(buf, buf, buf, 1, 3, 8, 8, 8, 8, 1, 1, 3, 1, 0, None), b"pad=fill needs fill values")
+
+    def grid_bwd(gout=buf, gsrc=buf, ggrid=buf):
+        return lib.km_grid_sample2d_bwd(gout, buf, buf, gsrc, ggrid, 1, 3, 8, 8, 8, 8, 1, 1, 0, 1, 0, None)
+
+    rejected(grid_bwd(gout=None), b"km_grid_sample2d_bwd: null gout")
+    assert grid_bwd(gsrc=None, ggrid=None) == 0
+
+    def loss(W=8, dtype=0):
+        return lib.km_warp_masked_loss(buf, buf, buf, buf, 1, 3, 8, W, 8, 8, 1, 0, 1, 1, 0, 0.0, dtype, None)
+
+    rejected(loss(dtype=1), b"dtype must be f32 / bf16 / f16")
+    rejected(loss(W=1), b"at least two columns")
+
+    modes = [(interp, pad, dtype) for interp in range(3) for pad in range(4) for dtype in range(4)]
+    for interp, pad, dtype in modes:
+        owner = interp == 1 and pad in (0, 3) and dtype != 1
+        assert lib.km_warp2d_bwd_needs_zero_init(interp, pad, dtype) == (0 if owner else 1), (interp, pad, dtype)
+    shapes = [(2, 3, 65, 64, 7, 9), (1, 1, 1, 1, 1, 1), (3, 4, 130, 200, 64, 64), (2, 5, 64, 64, 8, 8), (2, 2, 64, 65, 8, 8), (0, 3, 8, 8, 8, 8),
+              (1, 3, 8, 8, 0, 8), (1, 3, 32768, 32768, 8, 8), (1, 3, 8, 8, 32768, 32768), (1, 3, 32767, 32768, 8, 8)]
+    for B, C, H, W, h, w in shapes:
+        for interp, pad, dtype in modes:
+            none = (min(B, C, H, W, h, w) <= 0 or interp != 1 or dtype == 1 or (pad in (1, 2) and dtype != 0) or (pad == 3 and C not in (1, 3))
+                    or 4 * H * W >= 2**32 or 4 * h * w >= 2**32)
+            want = 0 if none else 80 * -(-W // 64) * -(-H // 64) * B * max(C // 3, C % 3)
+            assert lib.km_warp2d_bwd_workspace_bytes(B, C, H, W, h, w, interp, pad, dtype) == want, (B, C, H, W, h, w, interp, pad, dtype)
+
+
 def test_no_cpu_fallback():
     import kornia_amd as K
 
