@@ -27,8 +27,12 @@ class NativeLibraryError(RuntimeError):
 
 _P = c_void_p
 _I = c_int
-# name -> argtypes; every entry point returns int (0 ok, <0 bad argument, >0 hipError_t)
+# name -> argtypes; every entry point returns int (0 ok, <0 bad argument, >0 hipError_t) but those in _RESTYPE
 _PROTOTYPES = {
+    "km_device_info": [c_char_p, _I],
+    "km_set_traversal": [_I],
+    "km_config_set": [c_char_p, _I],
+    "km_config_get": [c_char_p],
     "km_homography_chain_fwd": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "km_homography_chain_bwd": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "km_perspective_transform_fwd": [_P, _P, _P, _I, _I, _P],
@@ -85,6 +89,7 @@ _PROTOTYPES = {
     "km_bilateral_blur_fwd": [_P] * 6 + [_I] * 12 + [_P],
     "km_bilateral_blur_bwd": [_P] * 9 + [_I] * 12 + [_P],
 }
+_RESTYPE = {"km_warp2d_bwd_workspace_bytes": ctypes.c_longlong}
 ABI_FEATURES = 15  # the km_abi_features() bits this binding calls
 _FEATURE_SYMBOLS = {"km_warp2d_pair_fwd": 1, "km_perspective_params_chain_fwd": 1, "km_inverse_chain_fwd": 1, "km_crop_resize_fwd": 2,
                     "km_median_blur_supported": 4, "km_median_blur_fwd": 4, "km_median_blur_bwd": 4, "km_bilateral_blur_fwd": 8, "km_bilateral_blur_bwd": 8}
@@ -120,10 +125,7 @@ def lib() -> ctypes.CDLL:
     got = handle.km_abi_version()
     if got != ABI_VERSION:
         raise NativeLibraryError(f"{LIB_PATH} has ABI version {got}, expected {ABI_VERSION}; rebuild it")
-    feat = getattr(handle, "km_abi_features", None)  # (new after set 3: absent means 0)
-    if feat is not None:
-        feat.restype = c_int
-    have = feat() if feat is not None else 0
+    have = _features_of(handle)
     if have & ABI_FEATURES != ABI_FEATURES:
         raise NativeLibraryError(f"{LIB_PATH} announces ABI features {have:#x}, expected {ABI_FEATURES:#x}; rebuild it")
     for name, argtypes in _PROTOTYPES.items():
@@ -131,21 +133,13 @@ def lib() -> ctypes.CDLL:
         if fn is None:
             raise NativeLibraryError(f"{LIB_PATH} does not export {name}; rebuild it")
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_longlong if name == "km_warp2d_bwd_workspace_bytes" else c_int
-    handle.km_device_info.argtypes = [c_char_p, c_int]
-    handle.km_device_info.restype = c_int
-    handle.km_set_traversal.argtypes = [c_int]
-    handle.km_set_traversal.restype = c_int
-    handle.km_config_set.argtypes = [c_char_p, c_int]
-    handle.km_config_set.restype = c_int
-    handle.km_config_get.argtypes = [c_char_p]
-    handle.km_config_get.restype = c_int
+        fn.restype = _RESTYPE.get(name, c_int)
     _lib = handle
     return handle
 
 
 def exported_symbols() -> list[str]:
-    return ["km_abi_version", "km_abi_features", "km_last_error", "km_device_info", "km_set_traversal", "km_config_set", "km_config_get", *_PROTOTYPES.keys()]
+    return ["km_abi_version", "km_abi_features", "km_last_error", *_PROTOTYPES]
 
 
 def check(rc: int, what: str) -> None:
@@ -154,10 +148,32 @@ def check(rc: int, what: str) -> None:
         raise NativeLibraryError(f"{what} failed (rc={rc}): {msg}")
 
 
+def launch(name: str, device: torch.device, *args) -> None:
+    """One native launch: entry point ``name`` with ``args`` and, last, the current stream of ``device``, under ``device_guard(device)``;
+    a non-zero return raises what ``check`` raises.  (``lib``, ``stream_ptr`` and ``device_guard`` are looked up at every call: the test
+    infrastructure replaces them by assignment.)"""
+    guard = device_guard(device)
+    if guard is _NO_GUARD:  # the current device, the common case: nothing to enter (two Python calls less - what this frame costs more)
+        rc = getattr(lib(), name)(*args, stream_ptr(device))
+    else:
+        with guard:
+            rc = getattr(lib(), name)(*args, stream_ptr(device))
+    if rc != 0:
+        check(rc, name)
+
+
+def _features_of(handle) -> int:
+    """``km_abi_features()`` of a loaded handle; the symbol is newer than ABI set 3, so its absence means 0."""
+    fn = getattr(handle, "km_abi_features", None)
+    if fn is None:
+        return 0
+    fn.restype = c_int
+    return int(fn())
+
+
 def abi_features() -> int:
     """``km_abi_features()`` of the loaded library (0 when it predates the symbol)."""
-    fn = getattr(lib(), "km_abi_features", None)
-    return int(fn()) if fn is not None else 0
+    return _features_of(lib())
 
 
 def mask_dtype_code(dtype: torch.dtype) -> int:
@@ -235,7 +251,6 @@ def device_guard(device: torch.device):
 def flags(t, device, n=None):
     """A per-sample / per-stage switch as the contiguous uint8 array the kernels read (zero / non-zero): a bool tensor is reinterpreted
     in place and a uint8 tensor - what the parameter kernels write - is taken as it is (no launch), anything else goes through ``!= 0``."""
-    import torch
     t = t.detach().to(device=device).reshape(-1)
     if n is not None and t.numel() != n:
         raise ValueError(f"expected {n} switch entries, got {t.numel()}")

@@ -82,9 +82,7 @@ def select_samples(transformed: torch.Tensor, original: torch.Tensor, apply: Opt
     flags = apply.to(device=t.device, dtype=torch.uint8).contiguous()
     out = torch.empty_like(t)
     B = t.shape[0]
-    with N.device_guard(t.device):
-        N.check(N.lib().km_select_samples_fwd(t.data_ptr(), o.data_ptr(), flags.data_ptr(), out.data_ptr(), B, t.numel() // max(B, 1),
-                                              N.dtype_code(t.dtype), N.stream_ptr(t.device)), "km_select_samples_fwd")
+    N.launch("km_select_samples_fwd", t.device, t.data_ptr(), o.data_ptr(), flags.data_ptr(), out.data_ptr(), B, t.numel() // max(B, 1), N.dtype_code(t.dtype))
     return out
 
 
@@ -112,13 +110,11 @@ def gaussian_taps(sigma: torch.Tensor, kernel_size, apply: Optional[torch.Tensor
         prob = None if batch_prob is None else batch_prob.detach().to(device=s.device, dtype=torch.float32).reshape(-1).contiguous()
         if prob is not None and prob.numel() != B:
             raise ValueError(f"batch_prob has {prob.numel()} entries, expected the batch size {B}")
-        with N.device_guard(s.device):
-            N.check(N.lib().km_gaussian_taps_dtype_fwd(s.data_ptr(), int(s.dim() == 2), N.ptr(prob), tx.data_ptr(), ty.data_ptr(), B, kx, ky,
-                                                       N.dtype_code(round_to or torch.float32), N.stream_ptr(s.device)), "km_gaussian_taps_dtype_fwd")
+        N.launch("km_gaussian_taps_dtype_fwd", s.device, s.data_ptr(), int(s.dim() == 2), N.ptr(prob), tx.data_ptr(), ty.data_ptr(), B, kx, ky,
+                 N.dtype_code(round_to or torch.float32))
         return tx, ty
     flags = None if apply is None else N.flags(apply, s.device, B)
-    with N.device_guard(s.device):
-        N.check(N.lib().km_gaussian_taps_fwd(s.data_ptr(), N.ptr(flags), tx.data_ptr(), ty.data_ptr(), B, kx, ky, N.stream_ptr(s.device)), "km_gaussian_taps_fwd")
+    N.launch("km_gaussian_taps_fwd", s.device, s.data_ptr(), N.ptr(flags), tx.data_ptr(), ty.data_ptr(), B, kx, ky)
     return tx, ty
 
 
@@ -137,9 +133,7 @@ def _params_chain(entry: str, inputs, params: Mapping[str, Any], B: int, device,
     m = torch.empty(B, 9, device=device, dtype=torch.float32)
     M = torch.empty(B, 3, 3, device=device, dtype=torch.float32) if with_matrix else None
     apply = torch.empty(B, device=device, dtype=torch.uint8) if prob is not None else None
-    with N.device_guard(device):
-        N.check(getattr(N.lib(), entry)(*(t.data_ptr() for t in inputs), N.ptr(prob), N.ptr(M), m.data_ptr(), N.ptr(apply), B, int(height), int(width),
-                                        int(height), int(width), N.stream_ptr(device)), entry)
+    N.launch(entry, device, *(t.data_ptr() for t in inputs), N.ptr(prob), N.ptr(M), m.data_ptr(), N.ptr(apply), B, int(height), int(width), int(height), int(width))
     return m, M, apply
 
 
@@ -205,9 +199,7 @@ def inverse_chain(M: torch.Tensor, height: int, width: int, affine: bool) -> tor
     Mc = M.detach().to(torch.float32).reshape(-1, 3, 3).contiguous()
     B = Mc.shape[0]
     m = torch.empty(B, 9, device=Mc.device, dtype=torch.float32)
-    with N.device_guard(Mc.device):
-        N.check(N.lib().km_inverse_chain_fwd(Mc.data_ptr(), 2 if affine else 3, m.data_ptr(), B, int(height), int(width), N.stream_ptr(Mc.device)),
-                "km_inverse_chain_fwd")
+    N.launch("km_inverse_chain_fwd", Mc.device, Mc.data_ptr(), 2 if affine else 3, m.data_ptr(), B, int(height), int(width))
     return m
 
 
@@ -250,10 +242,8 @@ def warp_pair(image: Optional[torch.Tensor], mask: torch.Tensor, m: torch.Tensor
         fill = _prepare_fill(fv if isinstance(fv, torch.Tensor) else torch.full((C,), float(fv)), C, dev, torch.float32) if C else None
         mfill = _fill_vector(fv, Cm, dev)  # (one value, or one per mask channel: a per-colour fill has no meaning for a label mask)
     flags = N.flags(apply, dev, B) if apply is not None else None
-    with N.device_guard(dev):
-        N.check(N.lib().km_warp2d_pair_fwd(N.ptr(x), N.ptr(out), mk.data_ptr(), mout.data_ptr(), m.data_ptr(), N.ptr(flags), B, C, Cm, H, W,
-                                           1 if affine else 0, interp, pad, int(bool(align_corners)), N.ptr(fill), N.ptr(mfill), N.dtype_code(dt),
-                                           N.mask_dtype_code(mk.dtype), N.stream_ptr(dev)), "km_warp2d_pair_fwd")
+    N.launch("km_warp2d_pair_fwd", dev, N.ptr(x), N.ptr(out), mk.data_ptr(), mout.data_ptr(), m.data_ptr(), N.ptr(flags), B, C, Cm, H, W, 1 if affine else 0,
+             interp, pad, int(bool(align_corners)), N.ptr(fill), N.ptr(mfill), N.dtype_code(dt), N.mask_dtype_code(mk.dtype))
     return out, mout
 
 
@@ -276,9 +266,8 @@ def color_jitter(input: torch.Tensor, params: Mapping[str, Any], order: Optional
         apply = torch.empty(B, device=dev, dtype=torch.uint8) if prob is not None else None
         bf, cf, sf, hf = (f.contiguous() for f in (bf, cf, sf, hf))
         gray_ws = torch.empty(B, device=dev, dtype=torch.float64)  # the contrast stage's accumulators: zeroed by the same launch
-        with N.device_guard(dev):
-            N.check(N.lib().km_color_params_ws_fwd(bf.data_ptr(), cf.data_ptr(), sf.data_ptr(), hf.data_ptr(), N.ptr(prob), table.data_ptr(), enable.data_ptr(),
-                                                   N.ptr(apply), gray_ws.data_ptr(), B, N.stream_ptr(dev)), "km_color_params_ws_fwd")
+        N.launch("km_color_params_ws_fwd", dev, bf.data_ptr(), cf.data_ptr(), sf.data_ptr(), hf.data_ptr(), N.ptr(prob), table.data_ptr(), enable.data_ptr(),
+                 N.ptr(apply), gray_ws.data_ptr(), B)
         return color_jitter_from_table(input, table, enable, apply, order, gray_ws)
     enable = torch.stack([(bf != 0).any(), (cf != 1).any(), (sf != 1).any(), (hf != 0).any()])
     return _color_jitter(input, bf, cf, sf, hf, order, enable=enable, apply=_apply_mask(params, dev))

@@ -62,13 +62,12 @@ def _color_launch(x: torch.Tensor, params: torch.Tensor, enable: Optional[torch.
     # (gray_ws: a (B,) float64 workspace that the launch which made `params` has ALREADY zeroed - km_color_params_ws_fwd - instead of a fill launch here)
     gray_sum = (gray_ws if gray_ws is not None else torch.zeros(B, device=dev, dtype=torch.float64)) if CONTRAST in stages else None
     arr = (ctypes.c_int * max(len(stages), 1))(*stages)
-    with N.device_guard(dev):
-        if apply is None:
-            N.check(N.lib().km_color_jitter_fwd(x.data_ptr(), out.data_ptr(), params.data_ptr(), N.ptr(gray_sum), N.ptr(enable), arr, len(stages), B, H, W,
-                                                N.dtype_code(x.dtype), N.stream_ptr(dev)), "km_color_jitter_fwd")
-        else:
-            N.check(N.lib().km_color_jitter_fwd_masked(x.data_ptr(), out.data_ptr(), params.data_ptr(), N.ptr(gray_sum), N.ptr(enable), apply.data_ptr(), arr,
-                                                       len(stages), B, H, W, N.dtype_code(x.dtype), N.stream_ptr(dev)), "km_color_jitter_fwd_masked")
+    if apply is None:
+        N.launch("km_color_jitter_fwd", dev, x.data_ptr(), out.data_ptr(), params.data_ptr(), N.ptr(gray_sum), N.ptr(enable), arr, len(stages), B, H, W,
+                 N.dtype_code(x.dtype))
+    else:
+        N.launch("km_color_jitter_fwd_masked", dev, x.data_ptr(), out.data_ptr(), params.data_ptr(), N.ptr(gray_sum), N.ptr(enable), apply.data_ptr(), arr,
+                 len(stages), B, H, W, N.dtype_code(x.dtype))
     return out, x, params, gray_sum
 
 
@@ -95,9 +94,8 @@ class _ColorJitterFunction(torch.autograd.Function):
         gsum = torch.zeros(B, device=dev, dtype=torch.float64) if CONTRAST in stages else None
         gparams = torch.zeros(B, 4, device=dev, dtype=torch.float64) if ctx.needs_input_grad[1] else None
         arr = (ctypes.c_int * max(len(stages), 1))(*stages)
-        with N.device_guard(dev):
-            N.check(N.lib().km_color_jitter_bwd(x.data_ptr(), gy.data_ptr(), gx.data_ptr(), params.data_ptr(), N.ptr(gray_sum), N.ptr(gsum), N.ptr(gparams),
-                                                N.ptr(enable), N.ptr(apply), arr, len(stages), B, H, W, N.dtype_code(x.dtype), N.stream_ptr(dev)), "km_color_jitter_bwd")
+        N.launch("km_color_jitter_bwd", dev, x.data_ptr(), gy.data_ptr(), gx.data_ptr(), params.data_ptr(), N.ptr(gray_sum), N.ptr(gsum), N.ptr(gparams),
+                 N.ptr(enable), N.ptr(apply), arr, len(stages), B, H, W, N.dtype_code(x.dtype))
         return (gx if ctx.needs_input_grad[0] else None), (gparams.to(params.dtype) if gparams is not None else None), None, None, None, None
 
 

@@ -51,10 +51,8 @@ def _launch_fwd(xc, gc, space, coef, ky, kx, border, dist, with_wsum):
     B, C, H, W = xc.shape
     out = torch.empty_like(xc)
     wsum = torch.empty((B, H, W), device=xc.device, dtype=space.dtype) if with_wsum else None
-    with N.device_guard(xc.device):
-        N.check(N.lib().km_bilateral_blur_fwd(xc.data_ptr(), N.ptr(gc), space.data_ptr(), coef.data_ptr(), out.data_ptr(), N.ptr(wsum), B, C,
-                                              C if gc is None else gc.shape[1], H, W, space.shape[0], coef.shape[0], ky, kx, border, dist,
-                                              N.dtype_code(xc.dtype), N.stream_ptr(xc.device)), "km_bilateral_blur_fwd")
+    N.launch("km_bilateral_blur_fwd", xc.device, xc.data_ptr(), N.ptr(gc), space.data_ptr(), coef.data_ptr(), out.data_ptr(), N.ptr(wsum), B, C,
+             C if gc is None else gc.shape[1], H, W, space.shape[0], coef.shape[0], ky, kx, border, dist, N.dtype_code(xc.dtype))
     return out, wsum
 
 
@@ -81,10 +79,8 @@ class _BilateralFunction(torch.autograd.Function):
         g = gy.detach().to(xc.dtype).contiguous()
         gx = torch.empty_like(xc) if (ctx.needs_input_grad[0] or not joint) else None
         gg = torch.empty_like(gc) if (joint and ctx.needs_input_grad[1]) else None
-        with N.device_guard(xc.device):
-            N.check(N.lib().km_bilateral_blur_bwd(xc.data_ptr(), N.ptr(gc), space.data_ptr(), coef.data_ptr(), out.data_ptr(), wsum.data_ptr(), g.data_ptr(),
-                                                  N.ptr(gx), N.ptr(gg), B, C, gc.shape[1] if joint else C, H, W, space.shape[0], coef.shape[0], ky, kx,
-                                                  border, dist, N.dtype_code(xc.dtype), N.stream_ptr(xc.device)), "km_bilateral_blur_bwd")
+        N.launch("km_bilateral_blur_bwd", xc.device, xc.data_ptr(), N.ptr(gc), space.data_ptr(), coef.data_ptr(), out.data_ptr(), wsum.data_ptr(), g.data_ptr(),
+                 N.ptr(gx), N.ptr(gg), B, C, gc.shape[1] if joint else C, H, W, space.shape[0], coef.shape[0], ky, kx, border, dist, N.dtype_code(xc.dtype))
         return gx, gg, None, None, None, None, None, None
 
 

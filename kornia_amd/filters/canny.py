@@ -96,23 +96,19 @@ def _canny_tail_native(grads: torch.Tensor, low: float, high: float, hysteresis:
     flag back once per promotion step (canny.py:160); this one once per sweep - a few per image whatever the edge length."""
     B, _, _, H, W = grads.shape
     grads = grads.contiguous()
-    lib = N.lib()
     dev = grads.device
     magnitude = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
     edges = torch.empty_like(magnitude)
-    with N.device_guard(dev):
-        stream = N.stream_ptr(dev)
-        N.check(lib.km_canny_nms_fwd(grads.data_ptr(), magnitude.data_ptr(), edges.data_ptr(), B, H, W, float(low), float(high), float(eps), stream),
-                "km_canny_nms_fwd")
-        if hysteresis:
-            out = torch.empty_like(edges)
-            flag = torch.zeros(1, device=dev, dtype=torch.int32)
-            while True:
-                N.check(lib.km_canny_hysteresis_sweep(edges.data_ptr(), out.data_ptr(), flag.data_ptr(), B, H, W, stream), "km_canny_hysteresis_sweep")
-                if int(flag.item()) == 0:
-                    break
-                flag.zero_()
-            edges = out
+    N.launch("km_canny_nms_fwd", dev, grads.data_ptr(), magnitude.data_ptr(), edges.data_ptr(), B, H, W, float(low), float(high), float(eps))
+    if hysteresis:
+        out = torch.empty_like(edges)
+        flag = torch.zeros(1, device=dev, dtype=torch.int32)
+        while True:
+            N.launch("km_canny_hysteresis_sweep", dev, edges.data_ptr(), out.data_ptr(), flag.data_ptr(), B, H, W)
+            if int(flag.item()) == 0:
+                break
+            flag.zero_()
+        edges = out
     return magnitude, edges
 
 

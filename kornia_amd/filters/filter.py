@@ -53,9 +53,7 @@ class _Filter2dFunction(torch.autograd.Function):
         B, C, H, W = xc.shape
         Bk, kH, kW = kc.shape
         out = torch.empty(B, C, H if same else H - kH + 1, W if same else W - kW + 1, device=x.device, dtype=x.dtype)
-        with N.device_guard(x.device):
-            N.check(N.lib().km_filter2d_fwd(xc.data_ptr(), kc.data_ptr(), out.data_ptr(), B, C, H, W, Bk, kH, kW, border, same,
-                                            N.dtype_code(x.dtype), N.stream_ptr(x.device)), "km_filter2d_fwd")
+        N.launch("km_filter2d_fwd", x.device, xc.data_ptr(), kc.data_ptr(), out.data_ptr(), B, C, H, W, Bk, kH, kW, border, same, N.dtype_code(x.dtype))
         ctx.save_for_backward(xc, kc)
         ctx.cfg = (border, same)
         return out
@@ -68,18 +66,15 @@ class _Filter2dFunction(torch.autograd.Function):
         Bk, kH, kW = kc.shape
         g = gy.detach().to(xc.dtype).contiguous()
         gx = gk = None
-        lib = N.lib()
-        with N.device_guard(xc.device):
-            stream = N.stream_ptr(xc.device)
-            if ctx.needs_input_grad[0]:
-                gx = torch.empty_like(xc)
-                N.check(lib.km_filter2d_bwd_input(g.data_ptr(), kc.data_ptr(), gx.data_ptr(), B, C, H, W, Bk, kH, kW, border, same,
-                                                  N.dtype_code(xc.dtype), stream), "km_filter2d_bwd_input")
-            if ctx.needs_input_grad[1]:
-                gk64 = torch.zeros(Bk, kH, kW, device=xc.device, dtype=torch.float64)
-                N.check(lib.km_filter2d_bwd_kernel(g.data_ptr(), xc.data_ptr(), gk64.data_ptr(), B, C, H, W, Bk, kH, kW, border,
-                                                   same, N.dtype_code(xc.dtype), stream), "km_filter2d_bwd_kernel")
-                gk = gk64.to(kc.dtype)
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(xc)  # (xc's own device)
+            N.launch("km_filter2d_bwd_input", xc.device, g.data_ptr(), kc.data_ptr(), gx.data_ptr(), B, C, H, W, Bk, kH, kW, border, same,
+                     N.dtype_code(xc.dtype))
+        if ctx.needs_input_grad[1]:
+            gk64 = torch.zeros(Bk, kH, kW, device=xc.device, dtype=torch.float64)
+            N.launch("km_filter2d_bwd_kernel", xc.device, g.data_ptr(), xc.data_ptr(), gk64.data_ptr(), B, C, H, W, Bk, kH, kW, border, same,
+                     N.dtype_code(xc.dtype))
+            gk = gk64.to(kc.dtype)
         return gx, gk, None, None
 
 
@@ -91,9 +86,8 @@ def _filter2d_sep_launch(x: torch.Tensor, kx: torch.Tensor, ky: torch.Tensor, bo
     Bk, kW = kxc.shape
     kH = kyc.shape[1]
     out = torch.empty(B, C, H if same else H - kH + 1, W if same else W - kW + 1, device=x.device, dtype=x.dtype)
-    with N.device_guard(x.device):
-        N.check(N.lib().km_filter2d_sep_fwd(xc.data_ptr(), kxc.data_ptr(), kyc.data_ptr(), out.data_ptr(), B, C, H, W, Bk, kH, kW,
-                                            border, same, N.dtype_code(x.dtype), N.stream_ptr(x.device)), "km_filter2d_sep_fwd")
+    N.launch("km_filter2d_sep_fwd", x.device, xc.data_ptr(), kxc.data_ptr(), kyc.data_ptr(), out.data_ptr(), B, C, H, W, Bk, kH, kW, border, same,
+             N.dtype_code(x.dtype))
     return out, kxc, kyc
 
 
@@ -116,20 +110,15 @@ class _Filter2dSepFunction(torch.autograd.Function):
         kH = kyc.shape[1]
         g = gy.detach().to(dtype).contiguous()
         gx = torch.empty(B, C, H, W, device=g.device, dtype=dtype)
-        lib = N.lib()
-        code, stream = N.dtype_code(dtype), N.stream_ptr(g.device)
-        with N.device_guard(g.device):
-            if lib.km_filter2d_sep_supported(kH, kW, same, code) & 2:
-                N.check(lib.km_filter2d_sep_bwd_input(g.data_ptr(), kxc.data_ptr(), kyc.data_ptr(), gx.data_ptr(), B, C, H, W, Bk, kH,
-                                                      kW, border, same, code, stream), "km_filter2d_sep_bwd_input")
-            else:
-                # large kernels: the fused adjoint does not fit in LDS - adjoint of the column pass, then of the row pass
-                Wo = W if same else W - kW + 1
-                gt = torch.empty(B, C, H, Wo, device=g.device, dtype=dtype)
-                N.check(lib.km_filter2d_bwd_input(g.data_ptr(), kyc.data_ptr(), gt.data_ptr(), B, C, H, Wo, Bk, kH, 1, border, same, code,
-                                                  stream), "km_filter2d_bwd_input")
-                N.check(lib.km_filter2d_bwd_input(gt.data_ptr(), kxc.data_ptr(), gx.data_ptr(), B, C, H, W, Bk, 1, kW, border, same, code,
-                                                  stream), "km_filter2d_bwd_input")
+        code = N.dtype_code(dtype)
+        if N.lib().km_filter2d_sep_supported(kH, kW, same, code) & 2:
+            N.launch("km_filter2d_sep_bwd_input", g.device, g.data_ptr(), kxc.data_ptr(), kyc.data_ptr(), gx.data_ptr(), B, C, H, W, Bk, kH, kW, border, same, code)
+        else:
+            # large kernels: the fused adjoint does not fit in LDS - adjoint of the column pass, then of the row pass
+            Wo = W if same else W - kW + 1
+            gt = torch.empty(B, C, H, Wo, device=g.device, dtype=dtype)
+            N.launch("km_filter2d_bwd_input", g.device, g.data_ptr(), kyc.data_ptr(), gt.data_ptr(), B, C, H, Wo, Bk, kH, 1, border, same, code)
+            N.launch("km_filter2d_bwd_input", g.device, gt.data_ptr(), kxc.data_ptr(), gx.data_ptr(), B, C, H, W, Bk, 1, kW, border, same, code)
         return gx, None, None, None, None
 
 

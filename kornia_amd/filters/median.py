@@ -33,9 +33,7 @@ def _launch_fwd(xc: torch.Tensor, ky: int, kx: int, apply: Optional[torch.Tensor
     B, C, H, W = xc.shape
     out = torch.empty_like(xc)
     idx = torch.empty((B, C, H, W), device=xc.device, dtype=torch.uint8) if with_idx else None
-    with N.device_guard(xc.device):
-        N.check(N.lib().km_median_blur_fwd(xc.data_ptr(), out.data_ptr(), N.ptr(idx), N.ptr(apply), B, C, H, W, ky, kx, N.dtype_code(xc.dtype),
-                                           N.stream_ptr(xc.device)), "km_median_blur_fwd")
+    N.launch("km_median_blur_fwd", xc.device, xc.data_ptr(), out.data_ptr(), N.ptr(idx), N.ptr(apply), B, C, H, W, ky, kx, N.dtype_code(xc.dtype))
     return out, idx
 
 
@@ -60,9 +58,7 @@ class _MedianBlurFunction(torch.autograd.Function):
         B, C, H, W = idx.shape
         g = gy.detach().contiguous()
         gx = torch.empty_like(g)
-        with N.device_guard(g.device):
-            N.check(N.lib().km_median_blur_bwd(g.data_ptr(), idx.data_ptr(), N.ptr(apply), gx.data_ptr(), B, C, H, W, ky, kx, N.dtype_code(g.dtype),
-                                               N.stream_ptr(g.device)), "km_median_blur_bwd")
+        N.launch("km_median_blur_bwd", g.device, g.data_ptr(), idx.data_ptr(), N.ptr(apply), gx.data_ptr(), B, C, H, W, ky, kx, N.dtype_code(g.dtype))
         return gx, None, None, None
 
 

@@ -47,12 +47,9 @@ class _ChainFunction(torch.autograd.Function):
         Mc = M.detach().to(cdt).contiguous()
         B, rows = Mc.shape[0], Mc.shape[1]
         out = torch.empty(B, 9, device=M.device, dtype=cdt)
-        with N.device_guard(M.device):
-            rc = N.lib().km_homography_chain_fwd(
-                Mc.data_ptr(), rows, None if want_inverse else out.data_ptr(), out.data_ptr() if want_inverse else None,
-                B, int(src_size[0]), int(src_size[1]), int(dst_size[0]), int(dst_size[1]), N.dtype_code(cdt),
-                N.stream_ptr(M.device))
-        N.check(rc, "km_homography_chain_fwd")
+        N.launch("km_homography_chain_fwd", M.device, Mc.data_ptr(), rows, None if want_inverse else out.data_ptr(),
+                 out.data_ptr() if want_inverse else None, B, int(src_size[0]), int(src_size[1]), int(dst_size[0]), int(dst_size[1]),
+                 N.dtype_code(cdt))
         ctx.save_for_backward(Mc)
         ctx.cfg = (src_size, dst_size, want_inverse, M.dtype)
         return out.view(B, 3, 3).to(M.dtype)
@@ -71,11 +68,8 @@ class _ChainFunction(torch.autograd.Function):
         B, rows = Mc.shape[0], Mc.shape[1]
         gm = g.detach().to(torch.float64).contiguous().view(B, 9)
         gM = torch.empty_like(Mc)
-        with N.device_guard(Mc.device):
-            rc = N.lib().km_homography_chain_bwd(
-                Mc.data_ptr(), rows, gm.data_ptr(), gM.data_ptr(), B, int(src_size[0]), int(src_size[1]),
-                int(dst_size[0]), int(dst_size[1]), N.dtype_code(Mc.dtype), N.stream_ptr(Mc.device))
-        N.check(rc, "km_homography_chain_bwd")
+        N.launch("km_homography_chain_bwd", Mc.device, Mc.data_ptr(), rows, gm.data_ptr(), gM.data_ptr(), B, int(src_size[0]), int(src_size[1]),
+                 int(dst_size[0]), int(dst_size[1]), N.dtype_code(Mc.dtype))
         return gM.to(in_dtype), None, None, None
 
 

@@ -95,9 +95,7 @@ def get_perspective_transform(points_src: torch.Tensor, points_dst: torch.Tensor
             # one launch (km_perspective_transform_fwd, same formulas); inputs that need gradients take the expression below
             ps, pd = points_src.detach().to(work).contiguous(), points_dst.detach().to(work).contiguous()
             out = torch.empty(ps.shape[0], 3, 3, device=ps.device, dtype=work)
-            with N.device_guard(ps.device):
-                N.check(N.lib().km_perspective_transform_fwd(ps.data_ptr(), pd.data_ptr(), out.data_ptr(), ps.shape[0], N.dtype_code(work),
-                                                             N.stream_ptr(ps.device)), "km_perspective_transform_fwd")
+            N.launch("km_perspective_transform_fwd", ps.device, ps.data_ptr(), pd.data_ptr(), out.data_ptr(), ps.shape[0], N.dtype_code(work))
             return out.to(dtype)
     a, b, c, d, e, f, g, h = _square_to_quad(points_src.to(work))
     A, Bq, C, D, E, Fq, G, Hq = _square_to_quad(points_dst.to(work))
@@ -197,9 +195,7 @@ def _affine_matrix2d_native(translations, center, scale, angle, sx, sy):
     dev = translations.device
     args = [None if t is None else t.detach().to(cdt).contiguous() for t in (translations, center, scale, angle, sx, sy)]
     out = torch.empty(B, 3, 3, device=dev, dtype=cdt)
-    with N.device_guard(dev):
-        N.check(N.lib().km_affine_matrix2d_fwd(*[N.ptr(t) for t in args], out.data_ptr(), B, N.dtype_code(cdt), N.stream_ptr(dev)),
-                "km_affine_matrix2d_fwd")
+    N.launch("km_affine_matrix2d_fwd", dev, *[N.ptr(t) for t in args], out.data_ptr(), B, N.dtype_code(cdt))
     return out.to(dtype)
 
 

@@ -129,13 +129,10 @@ def crop_resize(image, mask, src, size, interpolation: str = "bilinear", align_c
             raise ValueError(f"a flip switch has {f.numel()} entries, expected the batch size {B}")
     out = torch.empty(B, x.shape[1], oh, ow, device=dev, dtype=x.dtype) if x is not None else None
     mout = torch.empty(B, mk.shape[1], oh, ow, device=dev, dtype=mk.dtype) if mk is not None else None
-    with N.device_guard(dev):
-        N.check(N.lib().km_crop_resize_fwd(N.ptr(x), N.ptr(out), N.ptr(mk), N.ptr(mout), N.ptr(s), N.ptr(fx), N.ptr(fy), int(flip_all), B,
-                                           x.shape[1] if x is not None else 0, mk.shape[1] if mk is not None else 0, H, W, oh, ow,
-                                           1 if interpolation == "bilinear" else 0, _CROP_RESIZE if compensation == "resize" else _CROP_PAD,
-                                           int(bool(align_corners)), N.dtype_code(dt), N.mask_dtype_code(mk.dtype) if mk is not None else 0,
-                                           N.stream_ptr(dev)),
-                "km_crop_resize_fwd")
+    N.launch("km_crop_resize_fwd", dev, N.ptr(x), N.ptr(out), N.ptr(mk), N.ptr(mout), N.ptr(s), N.ptr(fx), N.ptr(fy), int(flip_all), B,
+             x.shape[1] if x is not None else 0, mk.shape[1] if mk is not None else 0, H, W, oh, ow, 1 if interpolation == "bilinear" else 0,
+             _CROP_RESIZE if compensation == "resize" else _CROP_PAD, int(bool(align_corners)), N.dtype_code(dt),
+             N.mask_dtype_code(mk.dtype) if mk is not None else 0)
     return out, mout
 
 

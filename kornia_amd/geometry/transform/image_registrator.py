@@ -33,7 +33,6 @@ _LOSS_KIND = {"l1": 0, "mse": 1}
 class _MaskedWarpLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, src, dst, mat, kind: int, align: int, norm: int, threshold: float):
-        lib = N.lib()
         dev = src.device
         x, d = src.detach().contiguous(), dst.detach().contiguous()
         m = mat.detach().to(device=dev, dtype=torch.float32).contiguous().view(-1, 9)
@@ -45,17 +44,13 @@ class _MaskedWarpLoss(torch.autograd.Function):
             ctx.mat_shape, ctx.mat_dtype = mat.shape, mat.dtype
             return torch.full((), float("nan"), device=dev, dtype=src.dtype)
         acc = torch.zeros(B, 11, device=dev, dtype=torch.float64)  # per image: loss sum, selected count, d sum / d mat
-        with N.device_guard(dev):
-            N.check(lib.km_warp_masked_loss(x.data_ptr(), d.data_ptr(), m.data_ptr(), acc.data_ptr(), B, C, H, W, h, w, B_M,
-                                            COORD_HOMOGRAPHY, norm, align, kind, float(threshold), N.dtype_code(x.dtype),
-                                            N.stream_ptr(dev)), "km_warp_masked_loss")
+        N.launch("km_warp_masked_loss", dev, x.data_ptr(), d.data_ptr(), m.data_ptr(), acc.data_ptr(), B, C, H, W, h, w, B_M, COORD_HOMOGRAPHY, norm, align,
+                 kind, float(threshold), N.dtype_code(x.dtype))
         # the sums over the batch, the mean and the unit gradient: one small launch (was ~nine torch ops around an 86 us kernel)
         loss64 = torch.empty((), device=dev, dtype=torch.float64)
         loss32 = torch.empty((), device=dev, dtype=torch.float32) if src.dtype == torch.float32 else None  # (0-dim, returned as is: a view would forbid the caller's in-place ops)
         gm_unit = torch.empty(B_M, 9, device=dev, dtype=torch.float64)
-        with N.device_guard(dev):
-            N.check(lib.km_warp_masked_loss_finish(acc.data_ptr(), B, B_M, loss64.data_ptr(), N.ptr(loss32), gm_unit.data_ptr(), N.stream_ptr(dev)),
-                    "km_warp_masked_loss_finish")
+        N.launch("km_warp_masked_loss_finish", dev, acc.data_ptr(), B, B_M, loss64.data_ptr(), N.ptr(loss32), gm_unit.data_ptr())
         ctx.save_for_backward(gm_unit)
         ctx.mat_shape, ctx.mat_dtype = mat.shape, mat.dtype
         # 0 / 0 = nan when nothing is selected, like the mean of an empty selection
@@ -70,9 +65,7 @@ class _MaskedWarpLoss(torch.autograd.Function):
             dev = gm_unit.device
             g1 = gout.detach().contiguous()
             gm = torch.empty(gm_unit.shape, device=dev, dtype=ctx.mat_dtype)
-            with N.device_guard(dev):
-                N.check(N.lib().km_scale_f64(gm_unit.data_ptr(), g1.data_ptr(), N.dtype_code(g1.dtype), gm.data_ptr(), N.dtype_code(ctx.mat_dtype),
-                                             gm_unit.numel(), N.stream_ptr(dev)), "km_scale_f64")
+            N.launch("km_scale_f64", dev, gm_unit.data_ptr(), g1.data_ptr(), N.dtype_code(g1.dtype), gm.data_ptr(), N.dtype_code(ctx.mat_dtype), gm_unit.numel())
             return None, None, gm.view(ctx.mat_shape), None, None, None, None
         gm = gm_unit.view(-1, 3, 3) * gout.to(torch.float64)
         return None, None, gm.to(ctx.mat_dtype).view(ctx.mat_shape), None, None, None, None

@@ -55,7 +55,6 @@ class _Warp2dFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, src: torch.Tensor, mat: torch.Tensor, fill: Optional[torch.Tensor], cfg: _WarpCfg, apply: Optional[torch.Tensor] = None):
-        lib = N.lib()
         dev = src.device
         cdt = N.compute_dtype(src.dtype)
         x = src.detach().contiguous()
@@ -63,23 +62,18 @@ class _Warp2dFunction(torch.autograd.Function):
         B, C, H, W = x.shape
         h, w = cfg.dsize
         B_M = Mc.shape[0]
-        stream = N.stream_ptr(dev)
         out = torch.empty(B, C, h, w, device=dev, dtype=src.dtype)
-        with N.device_guard(dev):
-            if cfg.coord_mode == COORD_HOMOGRAPHY:
-                m = Mc.view(B_M, 9)
-            else:
-                m = torch.empty(B_M, 9, device=dev, dtype=cdt)
-                N.check(lib.km_homography_chain_fwd(Mc.data_ptr(), Mc.shape[1], None, m.data_ptr(), B_M, H, W, h, w,
-                                                    N.dtype_code(cdt), stream), "km_homography_chain_fwd")
-            if apply is None:
-                N.check(lib.km_warp2d_fwd(x.data_ptr(), m.data_ptr(), out.data_ptr(), B, C, H, W, h, w, B_M, cfg.coord_mode,
-                                          cfg.norm_coords, cfg.interp, cfg.pad, cfg.align, N.ptr(fill), N.dtype_code(src.dtype),
-                                          stream), "km_warp2d_fwd")
-            else:  # the augmentation layer's per-sample switch, folded into the launch (forward only: _warp refuses it under autograd)
-                N.check(lib.km_warp2d_fwd_masked(x.data_ptr(), m.data_ptr(), out.data_ptr(), apply.data_ptr(), B, C, H, W, h, w, B_M, cfg.coord_mode,
-                                                 cfg.norm_coords, cfg.interp, cfg.pad, cfg.align, N.ptr(fill), N.dtype_code(src.dtype),
-                                                 stream), "km_warp2d_fwd_masked")
+        if cfg.coord_mode == COORD_HOMOGRAPHY:
+            m = Mc.view(B_M, 9)
+        else:
+            m = torch.empty(B_M, 9, device=dev, dtype=cdt)
+            N.launch("km_homography_chain_fwd", dev, Mc.data_ptr(), Mc.shape[1], None, m.data_ptr(), B_M, H, W, h, w, N.dtype_code(cdt))
+        if apply is None:
+            N.launch("km_warp2d_fwd", dev, x.data_ptr(), m.data_ptr(), out.data_ptr(), B, C, H, W, h, w, B_M, cfg.coord_mode, cfg.norm_coords,
+                     cfg.interp, cfg.pad, cfg.align, N.ptr(fill), N.dtype_code(src.dtype))
+        else:  # the augmentation layer's per-sample switch, folded into the launch (forward only: _warp refuses it under autograd)
+            N.launch("km_warp2d_fwd_masked", dev, x.data_ptr(), m.data_ptr(), out.data_ptr(), apply.data_ptr(), B, C, H, W, h, w, B_M, cfg.coord_mode,
+                     cfg.norm_coords, cfg.interp, cfg.pad, cfg.align, N.ptr(fill), N.dtype_code(src.dtype))
         ctx.save_for_backward(x, Mc, m, fill)
         ctx.cfg = cfg
         ctx.mat_dtype = mat.dtype
@@ -102,7 +96,6 @@ def _warp2d_backward(gout: torch.Tensor, x: torch.Tensor, Mc: torch.Tensor, m: t
     h, w = cfg.dsize
     B_M = Mc.shape[0]
     g = gout.detach().to(x.dtype).contiguous()
-    stream = N.stream_ptr(dev)
     gmat = None
     # both gradients wanted - or the image gradient under border / reflection padding, where the tile-owner kernel replaces a scatter with
     # global atomics: a workspace lets the library take them from one read of grad_out (include/kornia_amd.h)
@@ -117,18 +110,15 @@ def _warp2d_backward(gout: torch.Tensor, x: torch.Tensor, Mc: torch.Tensor, m: t
         gsrc = (torch.zeros if zero else torch.empty)(B, C, H, W, device=dev, dtype=cdt)
     # (on the one-read path the first launch zeroes the fp64 accumulators itself: one fill launch less per step)
     gm = (torch.empty if ws is not None else torch.zeros)(B_M, 9, device=dev, dtype=torch.float64) if need_mat else None
-    with N.device_guard(dev):
-        N.check(lib.km_warp2d_bwd_ws(g.data_ptr(), x.data_ptr(), m.data_ptr(), N.ptr(gsrc), N.ptr(gm), B, C, H, W, h, w,
-                                     B_M, cfg.coord_mode, cfg.norm_coords, cfg.interp, cfg.pad, cfg.align, N.ptr(fill),
-                                     N.dtype_code(x.dtype), N.ptr(ws), ws_bytes, stream), "km_warp2d_bwd_ws")
-        if need_mat:
-            if cfg.coord_mode == COORD_HOMOGRAPHY:
-                gmat = gm.view(B_M, 3, 3).to(mat_dtype)
-            else:
-                gM = torch.empty_like(Mc)
-                N.check(lib.km_homography_chain_bwd(Mc.data_ptr(), Mc.shape[1], gm.data_ptr(), gM.data_ptr(), B_M, H,
-                                                    W, h, w, N.dtype_code(cdt), stream), "km_homography_chain_bwd")
-                gmat = gM.to(mat_dtype)
+    N.launch("km_warp2d_bwd_ws", dev, g.data_ptr(), x.data_ptr(), m.data_ptr(), N.ptr(gsrc), N.ptr(gm), B, C, H, W, h, w, B_M, cfg.coord_mode,
+             cfg.norm_coords, cfg.interp, cfg.pad, cfg.align, N.ptr(fill), N.dtype_code(x.dtype), N.ptr(ws), ws_bytes)
+    if need_mat:
+        if cfg.coord_mode == COORD_HOMOGRAPHY:
+            gmat = gm.view(B_M, 3, 3).to(mat_dtype)
+        else:
+            gM = torch.empty_like(Mc)  # (Mc's own device)
+            N.launch("km_homography_chain_bwd", dev, Mc.data_ptr(), Mc.shape[1], gm.data_ptr(), gM.data_ptr(), B_M, H, W, h, w, N.dtype_code(cdt))
+            gmat = gM.to(mat_dtype)
     if gsrc is not None and gsrc.dtype != x.dtype:
         gsrc = gsrc.to(x.dtype)
     return gsrc, gmat
@@ -139,16 +129,13 @@ class _GridSampleFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input: torch.Tensor, grid: torch.Tensor, interp: int, pad: int, align: int):
-        lib = N.lib()
         dev = input.device
         x = input.detach().contiguous()
         gr = grid.detach().contiguous()
         B, C, H, W = x.shape
         B_G, h, w, _ = gr.shape
         out = torch.empty(B, C, h, w, device=dev, dtype=x.dtype)
-        with N.device_guard(dev):
-            N.check(lib.km_grid_sample2d_fwd(x.data_ptr(), gr.data_ptr(), out.data_ptr(), B, C, H, W, h, w, B_G, interp, pad, align,
-                                             N.dtype_code(x.dtype), N.stream_ptr(dev)), "km_grid_sample2d_fwd")
+        N.launch("km_grid_sample2d_fwd", dev, x.data_ptr(), gr.data_ptr(), out.data_ptr(), B, C, H, W, h, w, B_G, interp, pad, align, N.dtype_code(x.dtype))
         ctx.save_for_backward(x, gr)
         ctx.cfg = (interp, pad, align)
         return out
@@ -157,7 +144,6 @@ class _GridSampleFunction(torch.autograd.Function):
     def backward(ctx, gout: torch.Tensor):
         x, gr = ctx.saved_tensors
         interp, pad, align = ctx.cfg
-        lib = N.lib()
         dev = x.device
         cdt = N.compute_dtype(x.dtype)
         B, C, H, W = x.shape
@@ -165,9 +151,8 @@ class _GridSampleFunction(torch.autograd.Function):
         g = gout.detach().to(x.dtype).contiguous()
         gsrc = torch.zeros(B, C, H, W, device=dev, dtype=cdt) if ctx.needs_input_grad[0] else None
         ggrid = torch.empty(B, h, w, 2, device=dev, dtype=cdt) if ctx.needs_input_grad[1] else None
-        with N.device_guard(dev):
-            N.check(lib.km_grid_sample2d_bwd(g.data_ptr(), x.data_ptr(), gr.data_ptr(), N.ptr(gsrc), N.ptr(ggrid), B, C, H, W, h, w, B_G,
-                                             interp, pad, align, N.dtype_code(x.dtype), N.stream_ptr(dev)), "km_grid_sample2d_bwd")
+        N.launch("km_grid_sample2d_bwd", dev, g.data_ptr(), x.data_ptr(), gr.data_ptr(), N.ptr(gsrc), N.ptr(ggrid), B, C, H, W, h, w, B_G, interp, pad,
+                 align, N.dtype_code(x.dtype))
         if gsrc is not None and gsrc.dtype != x.dtype:
             gsrc = gsrc.to(x.dtype)
         if ggrid is not None:
@@ -272,13 +257,12 @@ def _warp_affine_from_chain(src: torch.Tensor, m: torch.Tensor, mode: str, paddi
     out = torch.empty_like(x)
     if apply is not None:
         apply = N.flags(apply, dev, B)
-    with N.device_guard(dev):
-        if apply is None:
-            N.check(N.lib().km_warp2d_fwd(x.data_ptr(), m.data_ptr(), out.data_ptr(), B, C, H, W, H, W, B, COORD_AFFINE, 1, interp, pad,
-                                          int(bool(align_corners)), N.ptr(fill), N.dtype_code(x.dtype), N.stream_ptr(dev)), "km_warp2d_fwd")
-        else:
-            N.check(N.lib().km_warp2d_fwd_masked(x.data_ptr(), m.data_ptr(), out.data_ptr(), apply.data_ptr(), B, C, H, W, H, W, B, COORD_AFFINE, 1, interp,
-                                                 pad, int(bool(align_corners)), N.ptr(fill), N.dtype_code(x.dtype), N.stream_ptr(dev)), "km_warp2d_fwd_masked")
+    if apply is None:
+        N.launch("km_warp2d_fwd", dev, x.data_ptr(), m.data_ptr(), out.data_ptr(), B, C, H, W, H, W, B, COORD_AFFINE, 1, interp, pad,
+                 int(bool(align_corners)), N.ptr(fill), N.dtype_code(x.dtype))
+    else:
+        N.launch("km_warp2d_fwd_masked", dev, x.data_ptr(), m.data_ptr(), out.data_ptr(), apply.data_ptr(), B, C, H, W, H, W, B, COORD_AFFINE, 1, interp,
+                 pad, int(bool(align_corners)), N.ptr(fill), N.dtype_code(x.dtype))
     return out
 
 

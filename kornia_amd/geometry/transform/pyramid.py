@@ -42,9 +42,7 @@ def _resize_adjoint(gy: torch.Tensor, shape, oh: int, ow: int, align: int, dtype
     B, C, H, W = shape
     g = gy.detach().to(dtype).contiguous()
     gx = torch.empty(B, C, H, W, device=g.device, dtype=dtype)
-    with N.device_guard(g.device):
-        N.check(N.lib().km_resize_bilinear_bwd(g.data_ptr(), gx.data_ptr(), B, C, H, W, oh, ow, align, N.dtype_code(dtype), N.stream_ptr(g.device)),
-                "km_resize_bilinear_bwd")
+    N.launch("km_resize_bilinear_bwd", g.device, g.data_ptr(), gx.data_ptr(), B, C, H, W, oh, ow, align, N.dtype_code(dtype))
     return gx
 
 
@@ -56,9 +54,7 @@ class _ResizeBilinearFunction(torch.autograd.Function):
         xc = x.detach().contiguous()
         B, C, H, W = xc.shape
         out = torch.empty(B, C, oh, ow, device=xc.device, dtype=xc.dtype)
-        with N.device_guard(xc.device):
-            N.check(N.lib().km_resize_bilinear_fwd(xc.data_ptr(), out.data_ptr(), B, C, H, W, oh, ow, align, N.dtype_code(xc.dtype),
-                                                   N.stream_ptr(xc.device)), "km_resize_bilinear_fwd")
+        N.launch("km_resize_bilinear_fwd", xc.device, xc.data_ptr(), out.data_ptr(), B, C, H, W, oh, ow, align, N.dtype_code(xc.dtype))
         ctx.cfg = ((B, C, H, W), oh, ow, align, xc.dtype)
         return out
 
@@ -77,9 +73,7 @@ class _PyrDownFunction(torch.autograd.Function):
         xc = x.detach().contiguous()
         B, C, H, W = xc.shape
         out = torch.empty(B, C, oh, ow, device=xc.device, dtype=xc.dtype)
-        with N.device_guard(xc.device):
-            N.check(N.lib().km_pyrdown_fwd(xc.data_ptr(), out.data_ptr(), B, C, H, W, oh, ow, border, align, N.dtype_code(xc.dtype),
-                                           N.stream_ptr(xc.device)), "km_pyrdown_fwd")
+        N.launch("km_pyrdown_fwd", xc.device, xc.data_ptr(), out.data_ptr(), B, C, H, W, oh, ow, border, align, N.dtype_code(xc.dtype))
         ctx.cfg = ((B, C, H, W), oh, ow, border, align, xc.dtype)
         return out
 
@@ -89,9 +83,7 @@ class _PyrDownFunction(torch.autograd.Function):
         g_blur = _resize_adjoint(gy, (B, C, H, W), oh, ow, align, dtype)
         taps = _get_pyramid_gaussian_kernel().to(device=gy.device, dtype=N.compute_dtype(dtype)).contiguous()
         gx = torch.empty_like(g_blur)
-        with N.device_guard(gy.device):
-            N.check(N.lib().km_filter2d_bwd_input(g_blur.data_ptr(), taps.data_ptr(), gx.data_ptr(), B, C, H, W, 1, 5, 5, border, 1,
-                                                  N.dtype_code(dtype), N.stream_ptr(gy.device)), "km_filter2d_bwd_input")
+        N.launch("km_filter2d_bwd_input", gy.device, g_blur.data_ptr(), taps.data_ptr(), gx.data_ptr(), B, C, H, W, 1, 5, 5, border, 1, N.dtype_code(dtype))
         return gx, None, None, None, None
 
 

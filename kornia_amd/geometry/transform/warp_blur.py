@@ -25,7 +25,6 @@ class _WarpBlurFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, src: torch.Tensor, mat: torch.Tensor, kx: torch.Tensor, ky: torch.Tensor, cfg: _WarpCfg, border: int):
-        lib = N.lib()
         dev = src.device
         cdt = N.compute_dtype(src.dtype)
         x = src.detach().contiguous()
@@ -34,14 +33,11 @@ class _WarpBlurFunction(torch.autograd.Function):
         h, w = cfg.dsize
         B_M = Mc.shape[0]
         K = kx.shape[1]
-        stream = N.stream_ptr(dev)
         out = torch.empty(B, C, h, w, device=dev, dtype=src.dtype)
-        with N.device_guard(dev):
-            m = torch.empty(B_M, 9, device=dev, dtype=cdt)
-            N.check(lib.km_homography_chain_fwd(Mc.data_ptr(), Mc.shape[1], None, m.data_ptr(), B_M, H, W, h, w, N.dtype_code(cdt), stream),
-                    "km_homography_chain_fwd")
-            N.check(lib.km_warp2d_blur_fwd(x.data_ptr(), m.data_ptr(), kx.data_ptr(), ky.data_ptr(), out.data_ptr(), B, C, H, W, h, w, B_M, kx.shape[0],
-                                           cfg.coord_mode, cfg.norm_coords, cfg.align, K, border, N.dtype_code(src.dtype), stream), "km_warp2d_blur_fwd")
+        m = torch.empty(B_M, 9, device=dev, dtype=cdt)
+        N.launch("km_homography_chain_fwd", dev, Mc.data_ptr(), Mc.shape[1], None, m.data_ptr(), B_M, H, W, h, w, N.dtype_code(cdt))
+        N.launch("km_warp2d_blur_fwd", dev, x.data_ptr(), m.data_ptr(), kx.data_ptr(), ky.data_ptr(), out.data_ptr(), B, C, H, W, h, w, B_M, kx.shape[0],
+                 cfg.coord_mode, cfg.norm_coords, cfg.align, K, border, N.dtype_code(src.dtype))
         ctx.save_for_backward(x, Mc, m, kx, ky)
         ctx.cfg, ctx.border, ctx.mat_dtype = cfg, border, mat.dtype
         return out
@@ -55,9 +51,9 @@ class _WarpBlurFunction(torch.autograd.Function):
         K = kx.shape[1]
         g = gy.detach().to(x.dtype).contiguous()
         gw = torch.empty(B, C, h, w, device=g.device, dtype=x.dtype)
-        with N.device_guard(g.device):  # the blur's adjoint (km_blur_fast.hip), then the warp's own backward
-            N.check(N.lib().km_filter2d_sep_bwd_input(g.data_ptr(), kx.data_ptr(), ky.data_ptr(), gw.data_ptr(), B, C, h, w, kx.shape[0], K, K,
-                                                      ctx.border, 1, N.dtype_code(x.dtype), N.stream_ptr(g.device)), "km_filter2d_sep_bwd_input")
+        # the blur's adjoint (km_blur_fast.hip), then the warp's own backward
+        N.launch("km_filter2d_sep_bwd_input", g.device, g.data_ptr(), kx.data_ptr(), ky.data_ptr(), gw.data_ptr(), B, C, h, w, kx.shape[0], K, K, ctx.border, 1,
+                 N.dtype_code(x.dtype))
         gsrc, gmat = _warp2d_backward(gw, x, Mc, m, None, cfg, ctx.mat_dtype, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return gsrc, gmat, None, None, None, None
 

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import functools
 import importlib
+import inspect
 import sys
 import threading
 import weakref
@@ -24,48 +25,23 @@ from . import enhance as _e
 from . import filters as _f
 from . import geometry as _g
 
-_NATIVE = {
-    "kornia.geometry.transform.imgwarp": {
-        "warp_perspective": _g.warp_perspective,
-        "warp_affine": _g.warp_affine,
-        "homography_warp": _g.homography_warp,
-        "warp_grid": _g.warp_grid,
-        "remap": _g.remap,
-        "get_affine_matrix2d": _g.get_affine_matrix2d,  # RandomAffine.compute_transformation: one launch instead of ~45
-        "get_perspective_transform": _g.get_perspective_transform,  # RandomPerspective / crops: one launch instead of ~40
-    },
-    # pyrdown as one fused launch (blur + decimation), pyrup on the native resize + 5x5 filter (SURVEY.md 8(f) rank 3)
-    "kornia.geometry.transform.pyramid": {"pyrdown": _g.transform.pyrdown, "pyrup": _g.transform.pyrup},
-    "kornia.geometry.linalg": {"transform_points": _g.transform_points},
-    "kornia.geometry.conversions": {"normalize_homography": _g.normalize_homography},
-    "kornia.filters.filter": {"filter2d": _f.filter2d, "filter2d_separable": _f.filter2d_separable},
-    "kornia.filters.gaussian": {"gaussian_blur2d": _f.gaussian_blur2d},
-    "kornia.filters.sobel": {"spatial_gradient": _f.spatial_gradient, "sobel": _f.sobel},
-    # blur + Sobel were already native through the two entries above; this one also replaces the ~25 elementwise / fixed-kernel
-    # convolution launches and the host-synchronised hysteresis loop behind them (km_canny_nms_fwd, km_canny_hysteresis_sweep)
-    "kornia.filters.canny": {"canny": _f.canny},
-    # one launch instead of the one-hot conv2d copy + torch.median; windows or dtypes the native op refuses stay on Kornia's own function
-    "kornia.filters.median": {"median_blur": _f.median_blur},
-    # one launch instead of pad + two unfold copies + ~ten elementwise passes; what the native op refuses (a 17 x 17 window, more than 16
-    # channels, sigma tensors that need a gradient) stays on Kornia's own function
-    "kornia.filters.bilateral": {"bilateral_blur": _f.bilateral_blur, "joint_bilateral_blur": _f.joint_bilateral_blur},
-    # fused colour kernels (the ColorJitter leg, SURVEY.md 8(f) rank 2)
-    "kornia.enhance.adjust": {
-        "adjust_brightness_accumulative": _e.adjust_brightness_accumulative,
-        "adjust_contrast_with_mean_subtraction": _e.adjust_contrast_with_mean_subtraction,
-        "adjust_saturation_with_gray_subtraction": _e.adjust_saturation_with_gray_subtraction,
-        "adjust_hue": _e.adjust_hue,
-    },
-}
-_COLOR_OPS = {id(f) for f in _NATIVE["kornia.enhance.adjust"].values()}
 _COLOR_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 _SUPPORTED = (torch.float32, torch.float64, torch.bfloat16, torch.float16)
 _patched: dict = {}  # id(original) -> (original, dispatcher)
 _patched_methods: list = []  # (class, attribute name, original function)
 
 
+def _compiling() -> bool:
+    return torch.jit.is_tracing() or torch.jit.is_scripting() or torch.compiler.is_compiling()
+
+
+def _native_image(t, dtypes=_COLOR_DTYPES, dim: int = 4) -> bool:
+    """a device tensor of rank ``dim`` and one of ``dtypes``"""
+    return isinstance(t, torch.Tensor) and _N.on_device(t) and t.dim() == dim and t.dtype in dtypes
+
+
 def _use_native(args, kwargs) -> bool:
-    if torch.jit.is_tracing() or torch.jit.is_scripting() or torch.compiler.is_compiling():
+    if _compiling():
         return False
     tensors = [a for a in list(args) + list(kwargs.values()) if isinstance(a, torch.Tensor)]
     if not tensors:
@@ -121,12 +97,49 @@ def _use_native_bilateral(joint: bool):
     return accept
 
 
-def _dispatcher(original: Callable, native: Callable) -> Callable:
-    if native is _f.bilateral_blur or native is _f.joint_bilateral_blur:
-        accept = _use_native_bilateral(native is _f.joint_bilateral_blur)
-    else:
-        accept = _use_native_color if id(native) in _COLOR_OPS else (_use_native_median if native is _f.median_blur else _use_native)
+_NATIVE = {
+    "kornia.geometry.transform.imgwarp": {
+        "warp_perspective": _g.warp_perspective,
+        "warp_affine": _g.warp_affine,
+        "homography_warp": _g.homography_warp,
+        "warp_grid": _g.warp_grid,
+        "remap": _g.remap,
+        "get_affine_matrix2d": _g.get_affine_matrix2d,  # RandomAffine.compute_transformation: one launch instead of ~45
+        "get_perspective_transform": _g.get_perspective_transform,  # RandomPerspective / crops: one launch instead of ~40
+    },
+    # pyrdown as one fused launch (blur + decimation), pyrup on the native resize + 5x5 filter (SURVEY.md 8(f) rank 3)
+    "kornia.geometry.transform.pyramid": {"pyrdown": _g.transform.pyrdown, "pyrup": _g.transform.pyrup},
+    "kornia.geometry.linalg": {"transform_points": _g.transform_points},
+    "kornia.geometry.conversions": {"normalize_homography": _g.normalize_homography},
+    "kornia.filters.filter": {"filter2d": _f.filter2d, "filter2d_separable": _f.filter2d_separable},
+    "kornia.filters.gaussian": {"gaussian_blur2d": _f.gaussian_blur2d},
+    "kornia.filters.sobel": {"spatial_gradient": _f.spatial_gradient, "sobel": _f.sobel},
+    # blur + Sobel were already native through the two entries above; this one also replaces the ~25 elementwise / fixed-kernel
+    # convolution launches and the host-synchronised hysteresis loop behind them (km_canny_nms_fwd, km_canny_hysteresis_sweep)
+    "kornia.filters.canny": {"canny": _f.canny},
+    # one launch instead of the one-hot conv2d copy + torch.median; windows or dtypes the native op refuses stay on Kornia's own function
+    "kornia.filters.median": {"median_blur": _f.median_blur},
+    # one launch instead of pad + two unfold copies + ~ten elementwise passes; what the native op refuses (a 17 x 17 window, more than 16
+    # channels, sigma tensors that need a gradient) stays on Kornia's own function
+    "kornia.filters.bilateral": {"bilateral_blur": _f.bilateral_blur, "joint_bilateral_blur": _f.joint_bilateral_blur},
+    # fused colour kernels (the ColorJitter leg, SURVEY.md 8(f) rank 2)
+    "kornia.enhance.adjust": {
+        "adjust_brightness_accumulative": _e.adjust_brightness_accumulative,
+        "adjust_contrast_with_mean_subtraction": _e.adjust_contrast_with_mean_subtraction,
+        "adjust_saturation_with_gray_subtraction": _e.adjust_saturation_with_gray_subtraction,
+        "adjust_hue": _e.adjust_hue,
+    },
+}
+# native function -> what its dispatcher asks of a call before it takes it (every other entry of _NATIVE: _use_native)
+_ACCEPT = {
+    **dict.fromkeys(_NATIVE["kornia.enhance.adjust"].values(), _use_native_color),
+    _f.median_blur: _use_native_median,
+    _f.bilateral_blur: _use_native_bilateral(False),
+    _f.joint_bilateral_blur: _use_native_bilateral(True),
+}
 
+
+def _dispatcher(original: Callable, native: Callable, accept: Callable) -> Callable:
     @functools.wraps(original)
     def wrapper(*args, **kwargs):
         if accept(args, kwargs):
@@ -150,10 +163,8 @@ def _color_jitter_apply(original: Callable) -> Callable:
     def apply_transform(self, input, params, flags, transform=None):
         keys = ("brightness_factor", "contrast_factor", "saturation_factor", "hue_factor")
         ok = (
-            isinstance(input, torch.Tensor) and _N.on_device(input) and input.dim() == 4 and input.shape[1] == 3
-            and input.dtype in _COLOR_DTYPES
-            and all(isinstance(params.get(k), torch.Tensor) for k in keys)
-            and not (torch.jit.is_tracing() or torch.jit.is_scripting() or torch.compiler.is_compiling())
+            _native_image(input) and input.shape[1] == 3 and all(isinstance(params.get(k), torch.Tensor) for k in keys)
+            and not _compiling()
         )
         order = None
         if ok:
@@ -198,12 +209,12 @@ def _registrator_level_loss(original: Callable) -> Callable:
         kind = "l1" if self.loss_fn is F.l1_loss else ("mse" if self.loss_fn is F.mse_loss else None)
         ok = (
             kind is not None and self.warper is hw_mod.HomographyWarper
-            and isinstance(img_src, torch.Tensor) and isinstance(img_dst, torch.Tensor) and _N.on_device(img_src) and _N.on_device(img_dst)
-            and img_src.dim() == 4 and img_src.shape == img_dst.shape and img_src.shape[-1] >= 2 and img_src.dtype in _COLOR_DTYPES
-            and img_src.dtype == img_dst.dtype and isinstance(transform_model, torch.Tensor) and transform_model.dim() == 3
+            and _native_image(img_src) and isinstance(img_dst, torch.Tensor) and _N.on_device(img_dst)
+            and img_src.shape == img_dst.shape and img_src.shape[-1] >= 2 and img_src.dtype == img_dst.dtype
+            and isinstance(transform_model, torch.Tensor) and transform_model.dim() == 3
             and transform_model.shape[-2:] == (3, 3) and transform_model.shape[0] in (1, img_src.shape[0])
             and not (torch.is_grad_enabled() and (img_src.requires_grad or img_dst.requires_grad))
-            and not (torch.jit.is_tracing() or torch.jit.is_scripting() or torch.compiler.is_compiling())
+            and not _compiling()
         )
         if not ok:
             return original(self, img_src, img_dst, transform_model)
@@ -255,14 +266,14 @@ def _blend_by_prob(original: Callable) -> Callable:
             and transformed.dim() >= 2 and to_apply.dim() == 1 and transformed.shape[0] == to_apply.shape[0]
             and transformed.dtype == not_transformed.dtype and transformed.dtype in _COLOR_DTYPES
             and not (torch.is_grad_enabled() and (transformed.requires_grad or not_transformed.requires_grad))
-            and not (torch.jit.is_tracing() or torch.jit.is_scripting() or torch.compiler.is_compiling())
+            and not _compiling()
         )
         if not ok:
             return original(transformed, not_transformed, to_apply)
         return select_samples(transformed, not_transformed, to_apply.to(transformed.device))
 
     blend.__wrapped__ = original
-    return staticmethod(blend)
+    return blend
 
 
 def _gaussian_blur_apply(original: Callable) -> Callable:
@@ -276,10 +287,9 @@ def _gaussian_blur_apply(original: Callable) -> Callable:
     def apply_transform(self, input, params, flags, transform=None):
         sigma = params.get("sigma") if hasattr(params, "get") else None
         ok = (
-            isinstance(input, torch.Tensor) and _N.on_device(input) and input.dim() == 4 and input.dtype in _COLOR_DTYPES
-            and isinstance(sigma, torch.Tensor) and sigma.dim() == 1 and flags.get("separable", True)
+            _native_image(input) and isinstance(sigma, torch.Tensor) and sigma.dim() == 1 and flags.get("separable", True)
             and not (torch.is_grad_enabled() and (input.requires_grad or sigma.requires_grad))
-            and not (torch.jit.is_tracing() or torch.jit.is_scripting() or torch.compiler.is_compiling())
+            and not _compiling()
         )
         if not ok:
             return original(self, input, params, flags, transform)
@@ -307,10 +317,9 @@ def _affine_compute(original: Callable) -> Callable:
     @functools.wraps(original)
     def compute_transformation(self, input, params, flags):
         ok = (
-            isinstance(input, torch.Tensor) and _N.on_device(input) and input.dim() == 4 and input.dtype in _COLOR_DTYPES
-            and all(isinstance(params.get(k), torch.Tensor) for k in keys)
+            _native_image(input) and all(isinstance(params.get(k), torch.Tensor) for k in keys)
             and not (torch.is_grad_enabled() and any(params[k].requires_grad for k in keys))
-            and not (torch.jit.is_tracing() or torch.jit.is_scripting() or torch.compiler.is_compiling())
+            and not _compiling()
         )
         if ok:
             B = input.shape[0]
@@ -353,11 +362,10 @@ def _geometric_apply(original: Callable, kind: str) -> Callable:
         if chain is not None:
             self._kornia_amd_chain = None
         ok = (
-            isinstance(input, torch.Tensor) and isinstance(transform, torch.Tensor) and _N.on_device(input) and _N.on_device(transform)
-            and input.dim() == 4 and input.dtype in _COLOR_DTYPES and transform.dim() == 3 and tuple(transform.shape[-2:]) == (3, 3)
-            and transform.shape[0] == input.shape[0] and transform.dtype in _SUPPORTED
+            _native_image(input) and _native_image(transform, _SUPPORTED, 3)
+            and tuple(transform.shape[-2:]) == (3, 3) and transform.shape[0] == input.shape[0]
             and not (torch.is_grad_enabled() and (input.requires_grad or transform.requires_grad))
-            and not (torch.jit.is_tracing() or torch.jit.is_scripting() or torch.compiler.is_compiling())
+            and not _compiling()
         )
         if not ok:
             return original(self, input, params, flags, transform)
@@ -408,6 +416,29 @@ def _geometric_apply(original: Callable, kind: str) -> Callable:
     return apply_transform
 
 
+_GEOMETRIC = "kornia.augmentation._2d.geometric."
+# (module, class, attribute, factory: Kornia's attribute -> its replacement), in the order they are installed
+_METHOD_HOOKS = (
+    # ColorJitter instances bind the four adjust functions at construction and wrap each in a torch.where:
+    # replace the method so that the whole sequence is one kernel
+    ("kornia.augmentation._2d.intensity.color_jitter", "ColorJitter", "apply_transform", _color_jitter_apply),
+    ("kornia.geometry.transform.image_registrator", "ImageRegistrator", "get_single_level_loss", _registrator_level_loss),
+    # the augmentation layer (SURVEY.md 8(f) rank 1): the probability blend of every augmentation and RandomGaussianBlur's apply step
+    ("kornia.augmentation.base", "_AugmentationBase", "transform_inputs", _transform_inputs),
+    ("kornia.augmentation.base", "_AugmentationBase", "_blend_by_prob", lambda static: staticmethod(_blend_by_prob(static.__func__))),
+    ("kornia.augmentation._2d.intensity.gaussian_blur", "RandomGaussianBlur", "apply_transform", _gaussian_blur_apply),
+    # the geometric leg of the same layer: the probability switch rides in the warp's own launch
+    # (RandomShear / RandomTranslate apply exactly like RandomAffine - _2d/geometric/shear.py:113-131, translate.py:102-120 -, RandomRotation
+    # through `affine` with zeros padding)
+    (_GEOMETRIC + "affine", "RandomAffine", "compute_transformation", _affine_compute),
+    (_GEOMETRIC + "affine", "RandomAffine", "apply_transform", functools.partial(_geometric_apply, kind="affine")),
+    (_GEOMETRIC + "perspective", "RandomPerspective", "apply_transform", functools.partial(_geometric_apply, kind="perspective")),
+    (_GEOMETRIC + "shear", "RandomShear", "apply_transform", functools.partial(_geometric_apply, kind="affine")),
+    (_GEOMETRIC + "translate", "RandomTranslate", "apply_transform", functools.partial(_geometric_apply, kind="affine")),
+    (_GEOMETRIC + "rotation", "RandomRotation", "apply_transform", functools.partial(_geometric_apply, kind="rotation")),
+)
+
+
 def patch() -> int:
     """Activate the native path inside Kornia. Returns the number of rebound module attributes.
 
@@ -430,7 +461,7 @@ def _patch_all() -> int:
         mod = importlib.import_module(mod_name)
         for name, native in table.items():
             original = getattr(mod, name)
-            _patched[id(original)] = (original, _dispatcher(original, native))
+            _patched[id(original)] = (original, _dispatcher(original, native, _ACCEPT.get(native, _use_native)))
     count = 0
     for mod_name, mod in list(sys.modules.items()):
         if mod is None or not (mod_name == "kornia" or mod_name.startswith("kornia.")):
@@ -440,45 +471,12 @@ def _patch_all() -> int:
             if hit is not None and value is hit[0]:
                 setattr(mod, attr, hit[1])
                 count += 1
-    # ColorJitter instances bind the four adjust functions at construction and wrap each in a torch.where:
-    # replace the method so that the whole sequence is one kernel
-    cj_mod = importlib.import_module("kornia.augmentation._2d.intensity.color_jitter")
-    original = cj_mod.ColorJitter.apply_transform
-    cj_mod.ColorJitter.apply_transform = _color_jitter_apply(original)
-    _patched_methods.append((cj_mod.ColorJitter, "apply_transform", original))
-    ir_mod = importlib.import_module("kornia.geometry.transform.image_registrator")
-    original = ir_mod.ImageRegistrator.get_single_level_loss
-    ir_mod.ImageRegistrator.get_single_level_loss = _registrator_level_loss(original)
-    _patched_methods.append((ir_mod.ImageRegistrator, "get_single_level_loss", original))
-    # the augmentation layer (SURVEY.md 8(f) rank 1): the probability blend of every augmentation and RandomGaussianBlur's apply step
-    base_mod = importlib.import_module("kornia.augmentation.base")
-    original = base_mod._AugmentationBase.transform_inputs
-    base_mod._AugmentationBase.transform_inputs = _transform_inputs(original)
-    _patched_methods.append((base_mod._AugmentationBase, "transform_inputs", original))
-    original = base_mod._AugmentationBase.__dict__["_blend_by_prob"]  # the staticmethod object itself
-    base_mod._AugmentationBase._blend_by_prob = _blend_by_prob(original.__func__)
-    _patched_methods.append((base_mod._AugmentationBase, "_blend_by_prob", original))
-    gb_mod = importlib.import_module("kornia.augmentation._2d.intensity.gaussian_blur")
-    original = gb_mod.RandomGaussianBlur.apply_transform
-    gb_mod.RandomGaussianBlur.apply_transform = _gaussian_blur_apply(original)
-    _patched_methods.append((gb_mod.RandomGaussianBlur, "apply_transform", original))
-    # the geometric leg of the same layer: the probability switch rides in the warp's own launch
-    # (RandomShear / RandomTranslate apply exactly like RandomAffine - _2d/geometric/shear.py:113-131, translate.py:102-120 -, RandomRotation
-    # through `affine` with zeros padding)
-    aff_mod = importlib.import_module("kornia.augmentation._2d.geometric.affine")
-    original = aff_mod.RandomAffine.compute_transformation
-    aff_mod.RandomAffine.compute_transformation = _affine_compute(original)
-    _patched_methods.append((aff_mod.RandomAffine, "compute_transformation", original))
-    for mod_name, cls_name, kind in (("kornia.augmentation._2d.geometric.affine", "RandomAffine", "affine"),
-                                     ("kornia.augmentation._2d.geometric.perspective", "RandomPerspective", "perspective"),
-                                     ("kornia.augmentation._2d.geometric.shear", "RandomShear", "affine"),
-                                     ("kornia.augmentation._2d.geometric.translate", "RandomTranslate", "affine"),
-                                     ("kornia.augmentation._2d.geometric.rotation", "RandomRotation", "rotation")):
+    for mod_name, cls_name, attr, factory in _METHOD_HOOKS:
         cls = getattr(importlib.import_module(mod_name), cls_name)
-        original = cls.apply_transform
-        cls.apply_transform = _geometric_apply(original, kind)
-        _patched_methods.append((cls, "apply_transform", original))
-    return count + 11
+        original = inspect.getattr_static(cls, attr)  # (a plain method: the function itself; _blend_by_prob: the staticmethod object)
+        setattr(cls, attr, factory(original))
+        _patched_methods.append((cls, attr, original))
+    return count + len(_METHOD_HOOKS)
 
 
 def unpatch() -> int:

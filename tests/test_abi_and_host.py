@@ -124,6 +124,116 @@ def test_warp_entry_points_host_contract_without_a_gpu():
             assert lib.km_warp2d_bwd_workspace_bytes(B, C, H, W, h, w, interp, pad, dtype) == want, (B, C, H, W, h, w, interp, pad, dtype)
 
 
+def test_launch_contract():
+    """_native.launch(name, device, *args): the entry point gets (*args, stream_ptr(device)) under exactly one device_guard(device); 0 returns
+    None without asking for the error text, anything else raises NativeLibraryError with the name, the code and km_last_error().  `lib`,
+    `stream_ptr` and `device_guard` are replaced AFTER import, as tests/emu/mode.py and tests/guarded_alloc.py do."""
+    from kornia_amd import _native as N
+
+    events = []
+
+    class Guard:
+        def __init__(self, device):
+            self.device = device
+
+        def __enter__(self):
+            events.append(("enter", self.device))
+
+        def __exit__(self, *exc):
+            events.append(("exit", self.device))
+            return False
+
+    class Lib:  # (hands the entry points out through __getattr__, like the recorder of tests/guarded_alloc.py)
+        rc = 0
+
+        def __getattr__(self, name):
+            if name == "km_last_error":
+                return lambda: events.append(("last_error",)) or b"fake: bad shape"
+            return lambda *args: events.append((name, args)) or self.rc
+
+    lib, dev = Lib(), torch.device("cuda", 3)
+    saved = N.lib, N.stream_ptr, N.device_guard
+    N.lib, N.stream_ptr, N.device_guard = (lambda: lib), (lambda device: ("stream of", device)), Guard
+    try:
+        assert N.launch("km_fake_fwd", dev, 1, None, 2.5) is None
+        assert events == [("enter", dev), ("km_fake_fwd", (1, None, 2.5, ("stream of", dev))), ("exit", dev)]
+        del events[:]
+        lib.rc = -7
+        with pytest.raises(N.NativeLibraryError) as err:
+            N.launch("km_fake_bwd", dev)
+        assert all(part in str(err.value) for part in ("km_fake_bwd", "rc=-7", "fake: bad shape"))
+        assert events == [("enter", dev), ("km_fake_bwd", (("stream of", dev),)), ("exit", dev), ("last_error",)]
+        try:
+            N.check(-7, "km_fake_bwd")
+        except N.NativeLibraryError as same:
+            assert str(same) == str(err.value)  # exactly what check(rc, name) raises
+    finally:
+        N.lib, N.stream_ptr, N.device_guard = saved
+
+
+def test_patch_installs_the_hook_table_and_unpatch_restores_it():
+    """patch() = the rebound module attributes + the eleven method hooks, each reachable as before; unpatch() puts every original object back."""
+    import sys
+    import types
+
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import ref_shim
+
+    if not ref_shim.reference_available():
+        pytest.skip("reference tree not present (GPU box)")
+    ref_shim.import_reference()
+    import importlib
+
+    import kornia_amd.kornia_patch as P
+
+    geometric = "kornia.augmentation._2d.geometric."
+    hooked = [("kornia.augmentation._2d.intensity.color_jitter", "ColorJitter", "apply_transform"),
+              ("kornia.geometry.transform.image_registrator", "ImageRegistrator", "get_single_level_loss"),
+              ("kornia.augmentation.base", "_AugmentationBase", "transform_inputs"),
+              ("kornia.augmentation.base", "_AugmentationBase", "_blend_by_prob"),
+              ("kornia.augmentation._2d.intensity.gaussian_blur", "RandomGaussianBlur", "apply_transform"),
+              (geometric + "affine", "RandomAffine", "compute_transformation"),
+              (geometric + "affine", "RandomAffine", "apply_transform"),
+              (geometric + "perspective", "RandomPerspective", "apply_transform"),
+              (geometric + "shear", "RandomShear", "apply_transform"),
+              (geometric + "translate", "RandomTranslate", "apply_transform"),
+              (geometric + "rotation", "RandomRotation", "apply_transform")]
+    classes = [(getattr(importlib.import_module(m), c), a) for m, c, a in hooked]
+
+    def kornia_modules():
+        return [mod for name, mod in list(sys.modules.items()) if mod is not None and (name == "kornia" or name.startswith("kornia."))]
+
+    def raw(cls, attr):  # (the object in the class's own namespace where it has one: a staticmethod stays a staticmethod)
+        return cls.__dict__[attr] if attr in cls.__dict__ else getattr(cls, attr)
+
+    assert not P.is_patched()
+    originals = [raw(cls, attr) for cls, attr in classes]
+    for mod_name, table in P._NATIVE.items():  # (patch() imports them before it scans)
+        importlib.import_module(mod_name)
+    targets = {id(getattr(sys.modules[m], name)): getattr(sys.modules[m], name) for m, table in P._NATIVE.items() for name in table}
+    rebound = sum(1 for mod in kornia_modules() for value in list(vars(mod).values()) if id(value) in targets and targets[id(value)] is value)
+    for _ in range(2):
+        n = P.patch()
+        try:
+            assert n == rebound + 11
+            assert [(cls, attr) for cls, attr, _ in P._patched_methods] == classes
+            for (cls, attr), original in zip(classes, originals):
+                assert raw(cls, attr) is not original
+                inner = original.__func__ if isinstance(original, staticmethod) else original
+                assert getattr(cls, attr).__wrapped__ is inner, (cls, attr)
+            assert isinstance(classes[3][0].__dict__["_blend_by_prob"], staticmethod)
+            dispatchers = [value for mod in kornia_modules() for value in vars(mod).values()
+                           if isinstance(value, types.FunctionType) and hasattr(value, "__kornia_amd_native__")]  # (functions only: no lazy module is touched)
+            assert len(dispatchers) == rebound
+            natives = {id(f) for table in P._NATIVE.values() for f in table.values()}
+            assert all(id(d.__wrapped__) in targets and id(d.__kornia_amd_native__) in natives for d in dispatchers)
+        finally:
+            assert P.unpatch() == n
+        assert not P.is_patched() and not P._patched_methods
+        assert all(raw(cls, attr) is original for (cls, attr), original in zip(classes, originals))
+        assert all(getattr(sys.modules[m], name) is targets[id(getattr(sys.modules[m], name))] for m, table in P._NATIVE.items() for name in table)
+
+
 def test_no_cpu_fallback():
     import kornia_amd as K
 
