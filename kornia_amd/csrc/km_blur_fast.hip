@@ -60,9 +60,6 @@ struct KmVec4<km_f16> {
     typedef uint2 V;
 };
 
-__device__ __forceinline__ float km_round_store(float v, const float*) { return v; }
-__device__ __forceinline__ float km_round_store(float v, const km_bf16*) { return __uint_as_float(((uint32_t)km_f32_to_bf16_bits(v)) << 16); }
-__device__ __forceinline__ float km_round_store(float v, const km_f16*) { KM_OPAQUE(v); return (float)(_Float16)v; }  // (never fused into the fma before it: km_common.h)
 
 
 template <typename T>
@@ -73,7 +70,7 @@ struct KmBlurArgs {
     const float* ky;  // (Bk, K)
     int C, H, W, Bk, border;
     uint32_t groups_x;   // W / 4
-    uint32_t bx, by;     // blocks per plane in x / y
+    uint32_t tiles_x, tiles_y;  // blocks per plane in x / y
     uint32_t nblocks;
     uint32_t reverse;    // the XCDs walk their block ranges backwards (km_traversal_next)
     uint32_t rows;       // strip height of the launch (host-side choice of the instantiation: KMB_ROWS, KMB_ROWS_MID or KMB_ROWS_SMALL)
@@ -107,11 +104,11 @@ template <typename T, int K, bool BWD, int ROWS = KMB_ROWS>
 __global__ __launch_bounds__(256, 1) void km_blur_reg_kernel(const KmBlurArgs<T> a) {
     constexpr int L = (K - 1) / 2, R = K - 1 - L;
     constexpr bool COLF = BWD && sizeof(T) == 2;  // column adjoint first, rounded to T (see the head of the file)
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks, a.reverse);
-    const uint32_t tbx = bid % a.bx;
-    bid /= a.bx;
-    const uint32_t tby = bid % a.by;
-    const uint32_t bc = bid / a.by;
+    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks, a.reverse);  // (km_tile_of spelled out: through the helper this kernel compiles to other code)
+    const uint32_t tbx = bid % a.tiles_x;
+    bid /= a.tiles_x;
+    const uint32_t tby = bid % a.tiles_y;
+    const uint32_t bc = bid / a.tiles_y;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (wave-uniform: the strip's rows are scalar values)
     const int gx = (int)tbx * 64 + lane;                      // column group (4 px)
     const int r0 = ((int)tby * 4 + wave) * ROWS;              // first output row of this thread's strip
@@ -239,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void km_blur_reg_kernel(const KmBlurArgs<T>
 #pragma unroll
                             for (int q = 0; q < K; ++q) acc = km_fma(kx[q], v[4 + o - L + q], acc);
                         }
-                        ring[kk][o] = km_round_store(acc, (const T*)nullptr);
+                        ring[kk][o] = km_round_as(acc, (const T*)nullptr);
                     }
                 }
                 // ---- column pass: emits output row r = r0 + it - (K-1) once K rows are in the window ----
@@ -255,14 +252,14 @@ __global__ __launch_bounds__(256, 1) void km_blur_reg_kernel(const KmBlurArgs<T>
                             float acc = 0.f;
 #pragma unroll
                             for (int d = 0; d < K; ++d) acc = km_fma(wy[d], ring[(kk + 1 + d) % K][o], acc);
-                            c4[o] = km_round_store(acc, (const T*)nullptr);
+                            c4[o] = km_round_as(acc, (const T*)nullptr);
                         }
 #pragma unroll
                         for (int j = 0; j < R; ++j) {
                             float acc = 0.f;
 #pragma unroll
                             for (int d = 0; d < K; ++d) acc = km_fma(wy[d], ring_e[(kk + 1 + d) % K][j], acc);
-                            ce[j] = km_round_store(acc, (const T*)nullptr);
+                            ce[j] = km_round_as(acc, (const T*)nullptr);
                         }
                         // row adjoint of the rounded column adjoint: columns c0 - 4 .. c0 + 7, the outer ones from the neighbour lanes
                         // (lane 0 / 63: their own edge columns), zero beyond the image
@@ -337,24 +334,23 @@ static int km_blur_rows(bool bwd, size_t elem, int K, uint64_t waves_big, int fo
 }
 
 template <typename T>
-static int km_blur_run(bool bwd, const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk,
-                       int K, int border, hipStream_t s) {
+static int km_blur_run(const KmFilterCall& c, bool bwd, const void* x, const void* kx, const void* ky, void* y) {
+    const int H = c.H, W = c.W, K = c.kH;
+    const uint64_t planes = (uint64_t)c.B * c.C;
+    const hipStream_t s = c.s;
     KmBlurArgs<T> a;
     a.x = (const T*)x; a.y = (T*)y; a.kx = (const float*)kx; a.ky = (const float*)ky;
-    a.C = C; a.H = H; a.W = W; a.Bk = Bk; a.border = border;
+    a.C = c.C; a.H = H; a.W = W; a.Bk = c.Bk; a.border = c.border;
     a.groups_x = (uint32_t)(W / 4);
-    a.bx = (a.groups_x + 63) / 64;
+    const uint32_t tiles_x = (a.groups_x + 63) / 64;
     const int force_rows = km_config().blur_rows;  // 8 / 16 / 32: forces the instantiation (tests, A/B timing: KM_BLUR_ROWS / km_config_set)
-    const uint64_t waves_big = (uint64_t)a.bx * (uint64_t)((H + KMB_ROWS - 1) / KMB_ROWS) * (uint64_t)B * C;
+    const uint64_t waves_big = (uint64_t)tiles_x * (uint64_t)((H + KMB_ROWS - 1) / KMB_ROWS) * planes;
     const int rows = km_blur_rows(bwd, sizeof(T), K, waves_big, force_rows);
     a.rows = (uint32_t)rows;
-    a.by = (uint32_t)((H + 4 * rows - 1) / (4 * rows));
-    const uint64_t nb = (uint64_t)a.bx * a.by * (uint64_t)B * C;
-    KM_REQUIRE(nb < (1ull << 31), "km_blur: grid too large");
-    a.nblocks = (uint32_t)nb;
-    if (nb == 0) return 0;
+    if (km_set_grid(a, tiles_x, (H + 4 * rows - 1) / (4 * rows), planes, "km_blur")) return -1;
+    if (a.nblocks == 0) return 0;
     a.reverse = km_traversal_next(s);
-    a.stream_out = km_stream_stores((uint64_t)B * C * H * W * sizeof(T));
+    a.stream_out = km_stream_stores(planes * H * W * sizeof(T));
     switch (K) {
         case 3: return km_blur_launch<T, 3>(bwd, a, s);
         case 5: return km_blur_launch<T, 5>(bwd, a, s);
@@ -364,8 +360,9 @@ static int km_blur_run(bool bwd, const void* x, const void* kx, const void* ky, 
 }
 
 // 1 if the register-tiled kernel handles this problem
-int km_blur_fast_supported(const void* x, const void* y, int H, int W, int kH, int kW, int border, int same, int dtype) {
-    if (!same || kH != kW || (kH & 1) == 0 || kH < 3 || kH > 9) return 0;
+int km_blur_fast_supported(const KmFilterCall& c, const void* x, const void* y) {
+    const int H = c.H, W = c.W, kH = c.kH, border = c.border, dtype = c.dtype;
+    if (!c.same || kH != c.kW || (kH & 1) == 0 || kH < 3 || kH > 9) return 0;
     if (dtype == KM_F64) return 0;
     if ((W & 3) != 0 || W < 8 || H < kH) return 0;
     if (border == KM_BORDER_REFLECT && (kH - 1) / 2 >= (H < W ? H : W)) return 0;
@@ -377,12 +374,11 @@ int km_blur_fast_supported(const void* x, const void* y, int H, int W, int kH, i
 
 // 1 if the register-tiled ADJOINT handles this problem: as above, except 16-bit circular borders (the column-first form takes the
 // neighbouring columns of a row from the neighbour lanes; a periodic row would need the wrapped chunk at both ends of a wave)
-int km_blur_fast_bwd_supported(const void* gy, const void* gx, int H, int W, int kH, int kW, int border, int same, int dtype) {
-    if (dtype != KM_F32 && border == KM_BORDER_CIRCULAR) return 0;
-    return km_blur_fast_supported(gy, gx, H, W, kH, kW, border, same, dtype);
+int km_blur_fast_bwd_supported(const KmFilterCall& c, const void* gy, const void* gx) {
+    if (c.dtype != KM_F32 && c.border == KM_BORDER_CIRCULAR) return 0;
+    return km_blur_fast_supported(c, gy, gx);
 }
 
-int km_blur_fast_run(bool bwd, const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk, int K,
-                     int border, int dtype, hipStream_t s) {
-    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_blur_run<KM_TAG_T(t)>(bwd, x, kx, ky, y, B, C, H, W, Bk, K, border, s); });
+int km_blur_fast_run(const KmFilterCall& c, bool bwd, const void* x, const void* kx, const void* ky, void* y) {
+    return km_dispatch_dtype<float, km_bf16, km_f16>(c.dtype, -1, [&](auto t) { return km_blur_run<KM_TAG_T(t)>(c, bwd, x, kx, ky, y); });
 }

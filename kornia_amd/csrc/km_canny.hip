@@ -34,11 +34,7 @@ __device__ __forceinline__ float kmc_mag_at(const float* g, size_t plane, int i,
 }
 
 __global__ __launch_bounds__(256) void km_canny_nms_kernel(const KmCannyArgs a) {
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t ty = bid % a.tiles_y;
-    const uint32_t b = bid / a.tiles_y;
+    const auto [tx, ty, b] = km_tile_of(a);
     const int j = (int)tx * 64 + (threadIdx.x & 63);
     const int i0 = (int)ty * 16 + (threadIdx.x >> 6) * 4;
     if (j >= a.W) return;
@@ -79,7 +75,7 @@ struct KmHystArgs {
 
 __global__ __launch_bounds__(256) void km_canny_hysteresis_kernel(const KmHystArgs a) {
     __shared__ uint8_t s[KMH_P * KMH_P];  // 0 none / 1 weak / 2 strong
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
+    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);  // (km_tile_of spelled out: through the helper this kernel compiles to other code)
     const uint32_t tx = bid % a.tiles_x;
     bid /= a.tiles_x;
     const uint32_t ty = bid % a.tiles_y;
@@ -139,11 +135,7 @@ int km_canny_nms_fwd(const void* grads, void* mag, void* edges, int B, int H, in
     a.grads = (const float*)grads; a.mag = (float*)mag; a.edges = (float*)edges;
     a.B = B; a.H = H; a.W = W;
     a.low = (float)low; a.high = (float)high; a.eps = (float)eps;
-    a.tiles_x = (uint32_t)((W + 63) / 64);
-    a.tiles_y = (uint32_t)((H + 15) / 16);
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B;
-    KM_REQUIRE(nb < (1ull << 31), "km_canny_nms_fwd: grid too large");
-    a.nblocks = (uint32_t)nb;
+    if (km_set_grid(a, (W + 63) / 64, (H + 15) / 16, (uint64_t)B, "km_canny_nms_fwd")) return -1;
     hipLaunchKernelGGL(km_canny_nms_kernel, dim3(a.nblocks), dim3(256), 0, (hipStream_t)stream, a);
     return km_check_launch("km_canny_nms_fwd");
 }
@@ -158,11 +150,7 @@ int km_canny_hysteresis_sweep(void* state, void* out, int* changed, int B, int H
     KmHystArgs a;
     a.state = (float*)state; a.out = (float*)out; a.changed = changed;
     a.B = B; a.H = H; a.W = W;
-    a.tiles_x = (uint32_t)((W + KMH_T - 1) / KMH_T);
-    a.tiles_y = (uint32_t)((H + KMH_T - 1) / KMH_T);
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B;
-    KM_REQUIRE(nb < (1ull << 31), "km_canny_hysteresis_sweep: grid too large");
-    a.nblocks = (uint32_t)nb;
+    if (km_set_grid(a, (W + KMH_T - 1) / KMH_T, (H + KMH_T - 1) / KMH_T, (uint64_t)B, "km_canny_hysteresis_sweep")) return -1;
     hipLaunchKernelGGL(km_canny_hysteresis_kernel, dim3(a.nblocks), dim3(256), 0, (hipStream_t)stream, a);
     return km_check_launch("km_canny_hysteresis_sweep");
 }

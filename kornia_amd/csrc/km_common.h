@@ -341,6 +341,32 @@ __device__ __forceinline__ uint32_t km_xcd_remap(uint32_t bid, uint32_t nblocks,
     return start + (reverse ? count - 1u - k : k);
 }
 
+// ---- tile grids: planes x tiles_y x tiles_x workgroups as one linear grid ---------------------------
+// Host: fills tiles_x / tiles_y / nblocks of any args struct that has them; 2^31 blocks or more fail with "<who>: grid too large".
+// (A caller whose grid can be empty returns 0 on a.nblocks == 0 itself.)
+template <typename A>
+static inline int km_set_grid(A& a, uint32_t tiles_x, uint32_t tiles_y, uint64_t planes, const char* who) {
+    a.tiles_x = tiles_x; a.tiles_y = tiles_y;
+    const uint64_t nb = (uint64_t)tiles_x * tiles_y * planes;
+    KM_REQUIRE(nb < (1ull << 31), "%s: grid too large", who);
+    a.nblocks = (uint32_t)nb;
+    return 0;
+}
+// Device: the workgroup's tile and plane after the XCD remap - `const auto [tx, ty, bc] = km_tile_of(a);`
+struct KmTile {
+    uint32_t tx, ty, bc;
+};
+template <typename A>
+__device__ __forceinline__ KmTile km_tile_of(const A& a, uint32_t reverse = 0u) {
+    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks, reverse);
+    KmTile t;
+    t.tx = bid % a.tiles_x;
+    bid /= a.tiles_x;
+    t.ty = bid % a.tiles_y;
+    t.bc = bid / a.tiles_y;
+    return t;
+}
+
 // LDS-DMA (gfx950 global_load_lds_dwordx4 / _dword): every lane names a 16-byte (4-byte) piece of global memory; the wave's pieces land in
 // LDS at lds_wave_base + lane * 16 (* 4) - straight from the memory pipe, no vector register, no ds_write.  Issued as inline assembly
 // (M0 carries the LDS byte address: saved, set, restored in the one statement), so the COMPILER DOES NOT KNOW the operation exists: it

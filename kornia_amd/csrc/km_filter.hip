@@ -23,22 +23,6 @@
 #include "km_regtile.h"
 
 
-struct KmFilterGeom {
-    int B, C, H, W, Bk, kH, kW, border, same;
-    int Ho, Wo;   // output size
-    int pt, pl;   // top / left padding ('same'), 0 for 'valid'
-};
-
-static KmFilterGeom km_filter_geom(int B, int C, int H, int W, int Bk, int kH, int kW, int border, int same) {
-    KmFilterGeom g;
-    g.B = B; g.C = C; g.H = H; g.W = W; g.Bk = Bk; g.kH = kH; g.kW = kW; g.border = border; g.same = same;
-    g.Ho = same ? H : H - kH + 1;
-    g.Wo = same ? W : W - kW + 1;
-    g.pt = same ? (kH - 1) / 2 : 0;
-    g.pl = same ? (kW - 1) / 2 : 0;
-    return g;
-}
-
 // =================================================================================================
 // fused separable forward
 // =================================================================================================
@@ -56,11 +40,6 @@ struct KmSepArgs {
     uint32_t tiles_x, tiles_y, nblocks;
 };
 
-// round an intermediate to the storage dtype (filter2d_separable stores out_x in input.dtype)
-__device__ __forceinline__ float km_round_to(float v, const float*) { return v; }
-__device__ __forceinline__ double km_round_to(double v, const double*) { return v; }
-__device__ __forceinline__ float km_round_to(float v, const km_bf16*) { return __uint_as_float(((uint32_t)km_f32_to_bf16_bits(v)) << 16); }
-__device__ __forceinline__ float km_round_to(float v, const km_f16*) { KM_OPAQUE(v); return (float)(km_f16)v; }
 
 template <typename T>
 __global__ __launch_bounds__(256) void km_filter_sep_fwd_kernel(const KmSepArgs<T> a) {
@@ -74,11 +53,7 @@ __global__ __launch_bounds__(256) void km_filter_sep_fwd_kernel(const KmSepArgs<
     R* s_kx = s_tmp + IH * KM_FS_TW;     // [kW]
     R* s_ky = s_kx + g.kW;               // [kH]
 
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t ty = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tx, ty, bc] = km_tile_of(a);
     const int b = bc / g.C;
     const int x0 = tx * KM_FS_TW, y0 = ty * KM_FS_TH;
     const T* img = a.x + (size_t)bc * g.H * g.W;
@@ -111,7 +86,7 @@ __global__ __launch_bounds__(256) void km_filter_sep_fwd_kernel(const KmSepArgs<
         const R* row = s_in + r * IW + c;
         R acc = 0;
         for (int q = 0; q < g.kW; ++q) acc = km_fma(s_kx[q], row[q], acc);
-        s_tmp[e] = km_round_to(acc, (const T*)nullptr);
+        s_tmp[e] = km_round_as(acc, (const T*)nullptr);
     }
     __syncthreads();
 
@@ -193,11 +168,7 @@ __global__ __launch_bounds__(256) void km_filter_sep_bwd_kernel(const KmSepArgs<
     R* s_kx = s_g2 + KM_FS_TH * EW;
     R* s_ky = s_kx + kW;
 
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t ty = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tx, ty, bc] = km_tile_of(a);
     const int b = bc / g.C;
     const int x0 = tx * KM_FS_TW, y0 = ty * KM_FS_TH;
     const T* gy = a.x + (size_t)bc * g.Ho * g.Wo;
@@ -236,7 +207,7 @@ __global__ __launch_bounds__(256) void km_filter_sep_bwd_kernel(const KmSepArgs<
         R acc = s_g1[(r + lt) * UW + c];
         if (g.same && p < g.H) acc += km_fold_sum(s_g1 + c, UW, y0 - lt, p, g.H, lt, rb, g.border);
         // 16-bit storage: the reference materialises this gradient in the input dtype
-        s_gi[e] = km_round_to(acc, (const T*)nullptr);
+        s_gi[e] = km_round_as(acc, (const T*)nullptr);
     }
     __syncthreads();
 
@@ -283,11 +254,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void km_filter2d_fwd_kernel(const KmFullArgs<T> a) {
     typedef typename KmTraits<T>::R R;
     const KmFilterGeom& g = a.g;
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t ty = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tx, ty, bc] = km_tile_of(a);
     const int b = bc / g.C;
     const int ox = tx * 64 + (threadIdx.x & 63);
     const int oy0 = ty * 16 + (threadIdx.x >> 6) * 4;
@@ -368,11 +335,7 @@ __device__ __forceinline__ typename KmTraits<T>::R km_f2d_adjoint_pixel(const Km
 template <typename T>
 __global__ __launch_bounds__(256) void km_filter2d_bwd_input_kernel(const KmFullArgs<T> a) {
     const KmFilterGeom& g = a.g;
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t ty = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tx, ty, bc] = km_tile_of(a);
     const int px = tx * 64 + (threadIdx.x & 63);
     const int py0 = ty * 16 + (threadIdx.x >> 6) * 4;
     if (px >= g.W) return;
@@ -434,17 +397,20 @@ __global__ __launch_bounds__(256) void km_filter2d_bwd_kernel_kernel(const KmFul
         km_atomic_add(a.gk + ((size_t)(b % g.Bk) * g.kH + p) * g.kW + q, (red[0] + red[1]) + (red[2] + red[3]));
 }
 
+
 // =================================================================================================
 // host side
 // =================================================================================================
-static int km_filter_validate(const char* fn, int B, int C, int H, int W, int Bk, int kH, int kW, int border, int same, int dtype) {
+// checks the arguments of a call and, when they pass, derives the output size and the padding
+static int km_filter_validate(const char* fn, KmFilterCall& c) {
+    const int B = c.B, C = c.C, H = c.H, W = c.W, Bk = c.Bk, kH = c.kH, kW = c.kW, border = c.border;
     KM_REQUIRE(B >= 0 && C >= 0 && H > 0 && W > 0, "%s: bad shape B=%d C=%d H=%d W=%d", fn, B, C, H, W);
     KM_REQUIRE((int64_t)H * W < (1ll << 31), "%s: image plane exceeds 2^31 elements", fn);
     KM_REQUIRE(kH > 0 && kW > 0, "%s: bad kernel size %dx%d", fn, kH, kW);
     KM_REQUIRE(Bk >= 1 && (B == 0 || B % Bk == 0), "%s: kernel batch %d must divide the input batch %d", fn, Bk, B);
     KM_REQUIRE(border >= 0 && border <= 3, "%s: bad border %d", fn, border);
-    KM_REQUIRE(dtype >= 0 && dtype <= 3, "%s: bad dtype %d", fn, dtype);
-    if (same) {
+    KM_REQUIRE(c.dtype >= 0 && c.dtype <= 3, "%s: bad dtype %d", fn, c.dtype);
+    if (c.same) {
         if (border == KM_BORDER_REFLECT)
             KM_REQUIRE(kH - 1 - (kH - 1) / 2 < H && kW - 1 - (kW - 1) / 2 < W, "%s: reflect padding must be smaller than the image", fn);
         if (border == KM_BORDER_CIRCULAR)
@@ -452,6 +418,10 @@ static int km_filter_validate(const char* fn, int B, int C, int H, int W, int Bk
     } else {
         KM_REQUIRE(kH <= H && kW <= W, "%s: 'valid' needs kernel <= image", fn);
     }
+    c.Ho = c.same ? H : H - kH + 1;
+    c.Wo = c.same ? W : W - kW + 1;
+    c.pt = c.same ? (kH - 1) / 2 : 0;
+    c.pl = c.same ? (kW - 1) / 2 : 0;
     return 0;
 }
 
@@ -472,53 +442,45 @@ static size_t km_sep_bwd_lds(int kH, int kW, int same) {
 #define KM_LDS_LIMIT (64 * 1024)
 
 template <typename T>
-static int km_sep_run(bool bwd, const void* x, const void* kx, const void* ky, void* y, const KmFilterGeom& g, hipStream_t s) {
+static int km_sep_run(const KmFilterCall& g, bool bwd, const void* x, const void* kx, const void* ky, void* y) {
     typedef typename KmTraits<T>::R R;
     KmSepArgs<T> a;
     a.x = (const T*)x; a.y = (T*)y; a.kx = (const R*)kx; a.ky = (const R*)ky; a.g = g;
     const int ow = bwd ? g.W : g.Wo, oh = bwd ? g.H : g.Ho;
-    a.tiles_x = (ow + KM_FS_TW - 1) / KM_FS_TW;
-    a.tiles_y = (oh + KM_FS_TH - 1) / KM_FS_TH;
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)g.B * g.C;
-    KM_REQUIRE(nb < (1ull << 31), "km_filter2d_sep: grid too large");
-    a.nblocks = (uint32_t)nb;
-    if (nb == 0) return 0;
+    if (km_set_grid(a, (ow + KM_FS_TW - 1) / KM_FS_TW, (oh + KM_FS_TH - 1) / KM_FS_TH, (uint64_t)g.B * g.C, "km_filter2d_sep")) return -1;
+    if (a.nblocks == 0) return 0;
     const size_t lds = bwd ? km_sep_bwd_lds<T>(g.kH, g.kW, g.same) : km_sep_fwd_lds<T>(g.kH, g.kW);
     KM_REQUIRE(lds <= KM_LDS_LIMIT, "km_filter2d_sep: kernel %dx%d needs %zu B of LDS (> %d); use the two-pass generic path", g.kH, g.kW, lds, KM_LDS_LIMIT);
     if (bwd)
-        hipLaunchKernelGGL(km_filter_sep_bwd_kernel<T>, dim3(a.nblocks), dim3(256), lds, s, a);
+        hipLaunchKernelGGL(km_filter_sep_bwd_kernel<T>, dim3(a.nblocks), dim3(256), lds, g.s, a);
     else
-        hipLaunchKernelGGL(km_filter_sep_fwd_kernel<T>, dim3(a.nblocks), dim3(256), lds, s, a);
+        hipLaunchKernelGGL(km_filter_sep_fwd_kernel<T>, dim3(a.nblocks), dim3(256), lds, g.s, a);
     return km_check_launch(bwd ? "km_filter2d_sep_bwd_input" : "km_filter2d_sep_fwd");
 }
 
 template <typename T>
-static int km_full_run(int which, const void* x, const void* gy, const void* k, void* y, double* gk, const KmFilterGeom& g, hipStream_t s) {
+static int km_full_run(const KmFilterCall& g, int which, const void* x, const void* gy, const void* k, void* y, double* gk) {
     typedef typename KmTraits<T>::R R;
     KmFullArgs<T> a;
     a.x = (const T*)x; a.gy = (const T*)gy; a.y = (T*)y; a.k = (const R*)k; a.gk = gk; a.g = g;
     if (which == 2) {
         if ((uint64_t)g.B * g.C == 0) return 0;
         KM_REQUIRE((uint64_t)g.kH * g.kW < 65536, "km_filter2d_bwd_kernel: kernel too large");
-        hipLaunchKernelGGL(km_filter2d_bwd_kernel_kernel<T>, dim3(g.B * g.C, g.kH * g.kW), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(km_filter2d_bwd_kernel_kernel<T>, dim3(g.B * g.C, g.kH * g.kW), dim3(256), 0, g.s, a);
         return km_check_launch("km_filter2d_bwd_kernel");
     }
     const int ow = which == 1 ? g.W : g.Wo, oh = which == 1 ? g.H : g.Ho;
-    a.tiles_x = (ow + 63) / 64;
-    a.tiles_y = (oh + 15) / 16;
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)g.B * g.C;
-    KM_REQUIRE(nb < (1ull << 31), "km_filter2d: grid too large");
-    a.nblocks = (uint32_t)nb;
-    if (nb == 0) return 0;
+    if (km_set_grid(a, (ow + 63) / 64, (oh + 15) / 16, (uint64_t)g.B * g.C, "km_filter2d")) return -1;
+    if (a.nblocks == 0) return 0;
     if (which == 0)
-        hipLaunchKernelGGL(km_filter2d_fwd_kernel<T>, dim3(a.nblocks), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(km_filter2d_fwd_kernel<T>, dim3(a.nblocks), dim3(256), 0, g.s, a);
     else
-        hipLaunchKernelGGL(km_filter2d_bwd_input_kernel<T>, dim3(a.nblocks), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(km_filter2d_bwd_input_kernel<T>, dim3(a.nblocks), dim3(256), 0, g.s, a);
     return km_check_launch(which == 0 ? "km_filter2d_fwd" : "km_filter2d_bwd_input");
 }
 
 template <typename T>
-static int km_full_frame_run(const void* gy, const void* k, void* gx, const KmFilterGeom& g, int pd, hipStream_t s) {
+static int km_full_frame_run(const KmFilterCall& g, const void* gy, const void* k, void* gx, int pd) {
     typedef typename KmTraits<T>::R R;
     KmFullArgs<T> a;
     a.x = nullptr; a.gy = (const T*)gy; a.y = (T*)gx; a.k = (const R*)k; a.gk = nullptr; a.g = g;
@@ -528,88 +490,80 @@ static int km_full_frame_run(const void* gy, const void* k, void* gx, const KmFi
     const uint64_t nb = (uint64_t)bpp * g.B * g.C;
     KM_REQUIRE(nb < (1ull << 31), "km_filter2d_bwd_input: grid too large");
     if (nb == 0) return 0;
-    hipLaunchKernelGGL(km_filter2d_bwd_frame_kernel<T>, dim3((uint32_t)nb), dim3(256), 0, s, a, pd, (uint32_t)frame, bpp);
+    hipLaunchKernelGGL(km_filter2d_bwd_frame_kernel<T>, dim3((uint32_t)nb), dim3(256), 0, g.s, a, pd, (uint32_t)frame, bpp);
     return km_check_launch("km_filter2d_bwd_input(frame)");
 }
 
-static int km_sep_algo() {
-    // KM_SEP_ALGO=lds forces the generic LDS-tiled kernels (debugging / A-B timing)
-    return km_config().sep_lds;
-}
-
 extern "C" {
+
+// (km_config().sep_lds below: KM_SEP_ALGO=lds forces the generic and the LDS-tiled kernels - debugging / A-B timing)
 
 // Replaces F.pad + F.conv2d(groups=Bk*C) of kornia/filters/filter.py:131-150.
 // k: prepared taps (Bk,kH,kW) in the compute dtype (fp32, or fp64 for f64 data).
 int km_filter2d_fwd(const void* x, const void* k, void* y, int B, int C, int H, int W, int Bk, int kH, int kW, int border,
                     int same, int dtype, void* stream) {
     if (B == 0 || C == 0) return 0;  // empty batch
-    if (km_filter_validate("km_filter2d_fwd", B, C, H, W, Bk, kH, kW, border, same, dtype)) return -1;
+    KmFilterCall c{{B, C, H, W, Bk, kH, kW, border, same}, dtype, (hipStream_t)stream};
+    if (km_filter_validate("km_filter2d_fwd", c)) return -1;
     KM_REQUIRE(x && k && y, "km_filter2d_fwd: null pointer");
-    if (km_sep_algo() == 0 && km_filter2d_fast_supported(x, y, H, W, kH, kW, border, same, dtype))
-        return km_filter2d_fast_run(x, k, y, B, C, H, W, Bk, kH, border, 0, dtype, (hipStream_t)stream);
-    const KmFilterGeom g = km_filter_geom(B, C, H, W, Bk, kH, kW, border, same);
-    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(0, x, nullptr, k, y, nullptr, g, (hipStream_t)stream); });
+    if (!km_config().sep_lds && km_filter2d_fast_supported(c, x, y)) return km_filter2d_fast_run(c, x, k, y, border, 0);
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(c, 0, x, nullptr, k, y, nullptr); });
 }
 
 // gradient wrt input (adjoint incl. the pad fold): gy (B,C,Ho,Wo) -> gx (B,C,H,W)
 int km_filter2d_bwd_input(const void* gy, const void* k, void* gx, int B, int C, int H, int W, int Bk, int kH, int kW,
                           int border, int same, int dtype, void* stream) {
     if (B == 0 || C == 0) return 0;  // empty batch
-    if (km_filter_validate("km_filter2d_bwd_input", B, C, H, W, Bk, kH, kW, border, same, dtype)) return -1;
+    KmFilterCall c{{B, C, H, W, Bk, kH, kW, border, same}, dtype, (hipStream_t)stream};
+    if (km_filter_validate("km_filter2d_bwd_input", c)) return -1;
     KM_REQUIRE(gy && k && gx, "km_filter2d_bwd_input: null pointer");
     KM_REQUIRE(!same || ((kH - 1 - (kH - 1) / 2) < KM_MAX_PRE && (kW - 1 - (kW - 1) / 2) < KM_MAX_PRE), "km_filter2d_bwd_input: kernel too large");
-    const KmFilterGeom g = km_filter_geom(B, C, H, W, Bk, kH, kW, border, same);
-    {
-        // square odd 3/5/7 kernels: interior by the register-tiled kernel on the zero-extended gradient with the rotated taps
-        // (for constant padding that is the whole adjoint), then the pad-wide frame by the exact pre-image kernel
-        // frame width: reflect folds padded coordinate -p onto pixel p for p = 1..pad, so pixels 0..pad are affected
-        const int pd = (kH - 1) / 2 + 1;
-        if (km_sep_algo() == 0 && km_filter2d_fast_supported(gy, gx, H, W, kH, kW, border, same, dtype) && H > 2 * pd && W > 2 * pd) {
-            const int rc = km_filter2d_fast_run(gy, k, gx, B, C, H, W, Bk, kH, KM_BORDER_CONSTANT, 1, dtype, (hipStream_t)stream);
-            if (rc != 0 || border == KM_BORDER_CONSTANT) return rc;
-            return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_frame_run<KM_TAG_T(t)>(gy, k, gx, g, pd, (hipStream_t)stream); });
-        }
+    // square odd 3/5/7 kernels: interior by the register-tiled kernel on the zero-extended gradient with the rotated taps
+    // (for constant padding that is the whole adjoint), then the pad-wide frame by the exact pre-image kernel
+    // frame width: reflect folds padded coordinate -p onto pixel p for p = 1..pad, so pixels 0..pad are affected
+    const int pd = (kH - 1) / 2 + 1;
+    if (!km_config().sep_lds && km_filter2d_fast_supported(c, gy, gx) && H > 2 * pd && W > 2 * pd) {
+        const int rc = km_filter2d_fast_run(c, gy, k, gx, KM_BORDER_CONSTANT, 1);
+        if (rc != 0 || border == KM_BORDER_CONSTANT) return rc;
+        return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_frame_run<KM_TAG_T(t)>(c, gy, k, gx, pd); });
     }
-    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(1, nullptr, gy, k, gx, nullptr, g, (hipStream_t)stream); });
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(c, 1, nullptr, gy, k, gx, nullptr); });
 }
 
 // gradient wrt the prepared taps: gk (Bk,kH,kW) fp64, pre-zeroed
 int km_filter2d_bwd_kernel(const void* gy, const void* x, void* gk, int B, int C, int H, int W, int Bk, int kH, int kW,
                            int border, int same, int dtype, void* stream) {
     if (B == 0 || C == 0) return 0;  // empty batch
-    if (km_filter_validate("km_filter2d_bwd_kernel", B, C, H, W, Bk, kH, kW, border, same, dtype)) return -1;
+    KmFilterCall c{{B, C, H, W, Bk, kH, kW, border, same}, dtype, (hipStream_t)stream};
+    if (km_filter_validate("km_filter2d_bwd_kernel", c)) return -1;
     KM_REQUIRE(gy && x && gk, "km_filter2d_bwd_kernel: null pointer");
-    if (km_sep_algo() == 0 && km_filter2d_fast_supported(x, gy, H, W, kH, kW, border, same, dtype))  // one pass instead of kH*kW
-        return km_filter2d_fast_tapgrad_run(gy, x, (double*)gk, B, C, H, W, Bk, kH, border, dtype, (hipStream_t)stream);
-    const KmFilterGeom g = km_filter_geom(B, C, H, W, Bk, kH, kW, border, same);
-    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(2, x, gy, nullptr, nullptr, (double*)gk, g, (hipStream_t)stream); });
+    if (!km_config().sep_lds && km_filter2d_fast_supported(c, x, gy))  // one pass instead of kH*kW
+        return km_filter2d_fast_tapgrad_run(c, gy, x, (double*)gk);
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(c, 2, x, gy, nullptr, nullptr, (double*)gk); });
 }
 
 // Replaces filter2d_separable (filter.py:155-207): kx (Bk,kW), ky (Bk,kH) in the compute dtype.
 int km_filter2d_sep_fwd(const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk, int kH,
                         int kW, int border, int same, int dtype, void* stream) {
     if (B == 0 || C == 0) return 0;  // empty batch
-    if (km_filter_validate("km_filter2d_sep_fwd", B, C, H, W, Bk, kH, kW, border, same, dtype)) return -1;
+    KmFilterCall c{{B, C, H, W, Bk, kH, kW, border, same}, dtype, (hipStream_t)stream};
+    if (km_filter_validate("km_filter2d_sep_fwd", c)) return -1;
     KM_REQUIRE(x && kx && ky && y, "km_filter2d_sep_fwd: null pointer");
-    if (km_sep_algo() == 0 && km_blur_fast_supported(x, y, H, W, kH, kW, border, same, dtype))
-        return km_blur_fast_run(false, x, kx, ky, y, B, C, H, W, Bk, kH, border, dtype, (hipStream_t)stream);
-    if (km_sep_algo() == 0 && km_filter_sep_big_supported(kH, kW, dtype))  // k >= 10: sliding-window LDS kernel
-        return km_filter_sep_big_run(x, kx, ky, y, B, C, H, W, Bk, kH, kW, border, same, dtype, (hipStream_t)stream);
-    const KmFilterGeom g = km_filter_geom(B, C, H, W, Bk, kH, kW, border, same);
-    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_sep_run<KM_TAG_T(t)>(false, x, kx, ky, y, g, (hipStream_t)stream); });
+    if (!km_config().sep_lds && km_blur_fast_supported(c, x, y)) return km_blur_fast_run(c, false, x, kx, ky, y);
+    if (!km_config().sep_lds && km_filter_sep_big_supported(kH, kW, dtype))  // k >= 10: sliding-window LDS kernel
+        return km_filter_sep_big_run(c, x, kx, ky, y);
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_sep_run<KM_TAG_T(t)>(c, false, x, kx, ky, y); });
 }
 
 int km_filter2d_sep_bwd_input(const void* gy, const void* kx, const void* ky, void* gx, int B, int C, int H, int W, int Bk,
                               int kH, int kW, int border, int same, int dtype, void* stream) {
     if (B == 0 || C == 0) return 0;  // empty batch
-    if (km_filter_validate("km_filter2d_sep_bwd_input", B, C, H, W, Bk, kH, kW, border, same, dtype)) return -1;
+    KmFilterCall c{{B, C, H, W, Bk, kH, kW, border, same}, dtype, (hipStream_t)stream};
+    if (km_filter_validate("km_filter2d_sep_bwd_input", c)) return -1;
     KM_REQUIRE(gy && kx && ky && gx, "km_filter2d_sep_bwd_input: null pointer");
-    if (km_sep_algo() == 0 && km_blur_fast_bwd_supported(gy, gx, H, W, kH, kW, border, same, dtype))
-        return km_blur_fast_run(true, gy, kx, ky, gx, B, C, H, W, Bk, kH, border, dtype, (hipStream_t)stream);
+    if (!km_config().sep_lds && km_blur_fast_bwd_supported(c, gy, gx)) return km_blur_fast_run(c, true, gy, kx, ky, gx);
     KM_REQUIRE(kH - 1 <= KM_FS_TH && kW - 1 <= KM_FS_TW, "km_filter2d_sep_bwd_input: kernel larger than the tile; use the generic path");
-    const KmFilterGeom g = km_filter_geom(B, C, H, W, Bk, kH, kW, border, same);
-    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_sep_run<KM_TAG_T(t)>(true, gy, kx, ky, gx, g, (hipStream_t)stream); });
+    return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_sep_run<KM_TAG_T(t)>(c, true, gy, kx, ky, gx); });
 }
 
 // Which fused separable kernels can take this kernel size (LDS budgets): bit 0 = forward (km_filter2d_sep_fwd),

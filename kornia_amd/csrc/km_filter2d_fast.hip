@@ -28,11 +28,7 @@ struct KmF2Args {
 template <typename T, int K>
 __global__ __launch_bounds__(256) void km_filter2d_reg_kernel(const KmF2Args<T> a) {
     constexpr int PD = (K - 1) / 2, NV = 4 + 2 * PD;
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tbx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t tby = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tbx, tby, bc] = km_tile_of(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gx = (int)tbx * 64 + lane;                  // column group (4 px)
     const int r0 = ((int)tby * 4 + wave) * KMF_ROWS;      // first output row of this wave's strip
@@ -107,17 +103,14 @@ __global__ __launch_bounds__(256) void km_filter2d_reg_kernel(const KmF2Args<T> 
 }
 
 template <typename T>
-static int kmf_run(const void* x, const void* k, void* y, int B, int C, int H, int W, int Bk, int K, int border, int flip, hipStream_t s) {
+static int kmf_run(const KmFilterCall& c, const void* x, const void* k, void* y, int border, int flip) {
     KmF2Args<T> a;
     a.x = (const T*)x; a.y = (T*)y; a.k = (const float*)k;
-    a.C = C; a.H = H; a.W = W; a.Bk = Bk; a.border = border; a.flip = flip;
-    a.tiles_x = (uint32_t)((W / 4 + 63) / 64);
-    a.tiles_y = (uint32_t)((H + 4 * KMF_ROWS - 1) / (4 * KMF_ROWS));
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B * C;
-    KM_REQUIRE(nb < (1ull << 31), "km_filter2d: grid too large");
-    a.nblocks = (uint32_t)nb;
-    if (nb == 0) return 0;
-    switch (K) {
+    a.C = c.C; a.H = c.H; a.W = c.W; a.Bk = c.Bk; a.border = border; a.flip = flip;
+    if (km_set_grid(a, (c.W / 4 + 63) / 64, (c.H + 4 * KMF_ROWS - 1) / (4 * KMF_ROWS), (uint64_t)c.B * c.C, "km_filter2d")) return -1;
+    if (a.nblocks == 0) return 0;
+    const hipStream_t s = c.s;
+    switch (c.kH) {
         case 3: hipLaunchKernelGGL((km_filter2d_reg_kernel<T, 3>), dim3(a.nblocks), dim3(256), 0, s, a); break;
         case 5: hipLaunchKernelGGL((km_filter2d_reg_kernel<T, 5>), dim3(a.nblocks), dim3(256), 0, s, a); break;
         default: hipLaunchKernelGGL((km_filter2d_reg_kernel<T, 7>), dim3(a.nblocks), dim3(256), 0, s, a); break;
@@ -144,11 +137,7 @@ template <typename T, int K>
 __global__ __launch_bounds__(256) void km_filter2d_tapgrad_reg_kernel(const KmF2GArgs<T> a) {
     constexpr int PD = (K - 1) / 2, NV = 4 + 2 * PD;
     __shared__ double red[4][K * K];
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tbx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t tby = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tbx, tby, bc] = km_tile_of(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gx = (int)tbx * 64 + lane;
     const int r0 = ((int)tby * 4 + wave) * KMF_ROWS;
@@ -230,17 +219,14 @@ __global__ __launch_bounds__(256) void km_filter2d_tapgrad_reg_kernel(const KmF2
 }
 
 template <typename T>
-static int kmf_tapgrad_run(const void* gy, const void* x, double* gk, int B, int C, int H, int W, int Bk, int K, int border, hipStream_t s) {
+static int kmf_tapgrad_run(const KmFilterCall& c, const void* gy, const void* x, double* gk) {
     KmF2GArgs<T> a;
     a.x = (const T*)x; a.gy = (const T*)gy; a.gk = gk;
-    a.C = C; a.H = H; a.W = W; a.Bk = Bk; a.border = border;
-    a.tiles_x = (uint32_t)((W / 4 + 63) / 64);
-    a.tiles_y = (uint32_t)((H + 4 * KMF_ROWS - 1) / (4 * KMF_ROWS));
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B * C;
-    KM_REQUIRE(nb < (1ull << 31), "km_filter2d_bwd_kernel: grid too large");
-    a.nblocks = (uint32_t)nb;
-    if (nb == 0) return 0;
-    switch (K) {
+    a.C = c.C; a.H = c.H; a.W = c.W; a.Bk = c.Bk; a.border = c.border;
+    if (km_set_grid(a, (c.W / 4 + 63) / 64, (c.H + 4 * KMF_ROWS - 1) / (4 * KMF_ROWS), (uint64_t)c.B * c.C, "km_filter2d_bwd_kernel")) return -1;
+    if (a.nblocks == 0) return 0;
+    const hipStream_t s = c.s;
+    switch (c.kH) {
         case 3: hipLaunchKernelGGL((km_filter2d_tapgrad_reg_kernel<T, 3>), dim3(a.nblocks), dim3(256), 0, s, a); break;
         case 5: hipLaunchKernelGGL((km_filter2d_tapgrad_reg_kernel<T, 5>), dim3(a.nblocks), dim3(256), 0, s, a); break;
         default: hipLaunchKernelGGL((km_filter2d_tapgrad_reg_kernel<T, 7>), dim3(a.nblocks), dim3(256), 0, s, a); break;
@@ -248,14 +234,14 @@ static int kmf_tapgrad_run(const void* gy, const void* x, double* gk, int B, int
     return km_check_launch("km_filter2d_bwd_kernel(reg)");
 }
 
-int km_filter2d_fast_tapgrad_run(const void* gy, const void* x, double* gk, int B, int C, int H, int W, int Bk, int K, int border, int dtype,
-                                 hipStream_t s) {
-    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmf_tapgrad_run<KM_TAG_T(t)>(gy, x, gk, B, C, H, W, Bk, K, border, s); });
+int km_filter2d_fast_tapgrad_run(const KmFilterCall& c, const void* gy, const void* x, double* gk) {
+    return km_dispatch_dtype<float, km_bf16, km_f16>(c.dtype, -1, [&](auto t) { return kmf_tapgrad_run<KM_TAG_T(t)>(c, gy, x, gk); });
 }
 
 // 1 if the register-tiled kernel handles this problem ('same', square odd 3/5/7, W % 4 == 0, 16-byte aligned, not fp64)
-int km_filter2d_fast_supported(const void* x, const void* y, int H, int W, int kH, int kW, int border, int same, int dtype) {
-    if (!same || kH != kW || !(kH == 3 || kH == 5 || kH == 7)) return 0;
+int km_filter2d_fast_supported(const KmFilterCall& c, const void* x, const void* y) {
+    const int H = c.H, W = c.W, kH = c.kH, border = c.border, dtype = c.dtype;
+    if (!c.same || kH != c.kW || !(kH == 3 || kH == 5 || kH == 7)) return 0;
     if (dtype == KM_F64) return 0;
     if ((W & 3) != 0 || W < 8 || H < 1) return 0;
     if (border == KM_BORDER_REFLECT && (kH - 1) / 2 >= (H < W ? H : W)) return 0;
@@ -265,8 +251,7 @@ int km_filter2d_fast_supported(const void* x, const void* y, int H, int W, int k
 }
 
 // flip = 0: y = correlate(x, k) with `border`;  flip = 1: the same with the taps rotated by 180 degrees - with
-// border = constant that is the exact adjoint of the constant-padded correlation, and the interior of every other one.
-int km_filter2d_fast_run(const void* x, const void* k, void* y, int B, int C, int H, int W, int Bk, int K, int border, int flip, int dtype,
-                         hipStream_t s) {
-    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kmf_run<KM_TAG_T(t)>(x, k, y, B, C, H, W, Bk, K, border, flip, s); });
+// border = constant (the argument, not the call's) that is the exact adjoint of the constant-padded correlation, and the interior of every other one.
+int km_filter2d_fast_run(const KmFilterCall& c, const void* x, const void* k, void* y, int border, int flip) {
+    return km_dispatch_dtype<float, km_bf16, km_f16>(c.dtype, -1, [&](auto t) { return kmf_run<KM_TAG_T(t)>(c, x, k, y, border, flip); });
 }

@@ -29,9 +29,6 @@ struct KmSepBigArgs {
     uint32_t tiles_x, tiles_y, nblocks;
 };
 
-__device__ __forceinline__ float kms_round_to(float v, const float*) { return v; }
-__device__ __forceinline__ float kms_round_to(float v, const km_bf16*) { return __uint_as_float(((uint32_t)km_f32_to_bf16_bits(v)) << 16); }
-__device__ __forceinline__ float kms_round_to(float v, const km_f16*) { KM_OPAQUE(v); return (float)(km_f16)v; }
 
 template <typename T>
 __global__ __launch_bounds__(256) void km_filter_sep_big_fwd_kernel(const KmSepBigArgs<T> a) {
@@ -42,11 +39,7 @@ __global__ __launch_bounds__(256) void km_filter_sep_big_fwd_kernel(const KmSepB
     float* s_tmp = s_in + (size_t)IH * IP;  // [IH][KMS_TW]
     __shared__ __attribute__((aligned(16))) float s_kx[72], s_ky[72];  // taps, zero-padded to a multiple of 8 (k <= 65)
 
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t ty = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tx, ty, bc] = km_tile_of(a);
     const int b = (int)(bc / a.C);
     const int x0 = (int)tx * KMS_TW, y0 = (int)ty * KMS_TH;
     const T* img = a.x + (size_t)bc * a.H * a.W;
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(256) void km_filter_sep_big_fwd_kernel(const KmSepB
             }
         }
 #pragma unroll
-        for (int o = 0; o < 4; ++o) s_tmp[r * KMS_TW + c0 + o] = kms_round_to(acc[o], (const T*)nullptr);
+        for (int o = 0; o < 4; ++o) s_tmp[r * KMS_TW + c0 + o] = km_round_as(acc[o], (const T*)nullptr);
     }
     __syncthreads();
 
@@ -203,27 +196,18 @@ int km_filter_sep_big_supported(int kH, int kW, int dtype) {
 }
 
 template <typename T>
-static int kms_run(const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk, int kH, int kW, int border,
-                   int same, hipStream_t s) {
+static int kms_run(const KmFilterCall& c, const void* x, const void* kx, const void* ky, void* y) {
     KmSepBigArgs<T> a;
     a.x = (const T*)x; a.y = (T*)y; a.kx = (const float*)kx; a.ky = (const float*)ky;
-    a.C = C; a.H = H; a.W = W; a.Bk = Bk; a.kH = kH; a.kW = kW; a.border = border; a.same = same;
-    a.Ho = same ? H : H - kH + 1;
-    a.Wo = same ? W : W - kW + 1;
-    a.pt = same ? (kH - 1) / 2 : 0;
-    a.pl = same ? (kW - 1) / 2 : 0;
-    const size_t lds = kms_lds_bytes(kH, kW, &a.iw_pitch);
-    a.tiles_x = (uint32_t)((a.Wo + KMS_TW - 1) / KMS_TW);
-    a.tiles_y = (uint32_t)((a.Ho + KMS_TH - 1) / KMS_TH);
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B * C;
-    KM_REQUIRE(nb < (1ull << 31), "km_filter2d_sep: grid too large");
-    a.nblocks = (uint32_t)nb;
-    if (nb == 0) return 0;
-    hipLaunchKernelGGL(km_filter_sep_big_fwd_kernel<T>, dim3(a.nblocks), dim3(256), lds, s, a);
+    a.C = c.C; a.H = c.H; a.W = c.W; a.Bk = c.Bk; a.kH = c.kH; a.kW = c.kW; a.border = c.border; a.same = c.same;
+    a.Ho = c.Ho; a.Wo = c.Wo; a.pt = c.pt; a.pl = c.pl;
+    const size_t lds = kms_lds_bytes(c.kH, c.kW, &a.iw_pitch);
+    if (km_set_grid(a, (c.Wo + KMS_TW - 1) / KMS_TW, (c.Ho + KMS_TH - 1) / KMS_TH, (uint64_t)c.B * c.C, "km_filter2d_sep")) return -1;
+    if (a.nblocks == 0) return 0;
+    hipLaunchKernelGGL(km_filter_sep_big_fwd_kernel<T>, dim3(a.nblocks), dim3(256), lds, c.s, a);
     return km_check_launch("km_filter2d_sep_fwd(big)");
 }
 
-int km_filter_sep_big_run(const void* x, const void* kx, const void* ky, void* y, int B, int C, int H, int W, int Bk, int kH, int kW,
-                          int border, int same, int dtype, hipStream_t s) {
-    return km_dispatch_dtype<float, km_bf16, km_f16>(dtype, -1, [&](auto t) { return kms_run<KM_TAG_T(t)>(x, kx, ky, y, B, C, H, W, Bk, kH, kW, border, same, s); });
+int km_filter_sep_big_run(const KmFilterCall& c, const void* x, const void* kx, const void* ky, void* y) {
+    return km_dispatch_dtype<float, km_bf16, km_f16>(c.dtype, -1, [&](auto t) { return kms_run<KM_TAG_T(t)>(c, x, kx, ky, y); });
 }

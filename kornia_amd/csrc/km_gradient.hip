@@ -30,7 +30,7 @@ __device__ __forceinline__ int km_clampi(int v, int lo, int hi) { return v < lo 
 template <typename T>
 __global__ __launch_bounds__(256) void km_spatial_gradient_fwd_kernel(const KmGradArgs<T> a) {
     typedef typename KmTraits<T>::R R;
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
+    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);  // (km_tile_of spelled out: through the helper the fp64 kernel compiles to other code)
     const uint32_t tx = bid % a.tiles_x;
     bid /= a.tiles_x;
     const uint32_t ty = bid % a.tiles_y;
@@ -93,11 +93,7 @@ __device__ __forceinline__ typename KmTraits<T>::R km_sg_adjoint_pixel(const KmG
 
 template <typename T>
 __global__ __launch_bounds__(256) void km_spatial_gradient_bwd_kernel(const KmGradArgs<T> a) {
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t ty = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tx, ty, bc] = km_tile_of(a);
     const int px = tx * 64 + (threadIdx.x & 63);
     const int py0 = ty * 16 + (threadIdx.x >> 6) * 4;
     if (px >= a.W) return;
@@ -141,11 +137,7 @@ __global__ __launch_bounds__(256) void km_spatial_gradient_bwd_frame_kernel(cons
 template <typename T, int KS, int NOUT>
 __global__ __launch_bounds__(256) void km_spatial_gradient_reg_kernel(const KmGradArgs<T> a) {
     constexpr int PD = KS / 2, NV = 4 + 2 * PD;
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tbx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t tby = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tbx, tby, bc] = km_tile_of(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gx = (int)tbx * 64 + lane;                     // column group (4 px)
     const int r0 = ((int)tby * 4 + wave) * KM_SG_ROWS;       // first output row of this wave's strip
@@ -223,11 +215,7 @@ __global__ __launch_bounds__(256) void km_spatial_gradient_reg_kernel(const KmGr
 template <typename T, int KS, int NOUT>
 __global__ __launch_bounds__(256) void km_spatial_gradient_bwd_reg_kernel(const KmGradArgs<T> a) {
     constexpr int PD = KS / 2, NV = 4 + 2 * PD;
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tbx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t tby = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tbx, tby, bc] = km_tile_of(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gx = (int)tbx * 64 + lane;
     const int r0 = ((int)tby * 4 + wave) * KM_SG_ROWS;
@@ -305,11 +293,7 @@ __global__ __launch_bounds__(256) void km_spatial_gradient_bwd_reg_kernel(const 
 template <typename T>
 static int km_sg_fast_bwd_launch(const KmGradArgs<T>& a0, hipStream_t s) {
     KmGradArgs<T> a = a0;
-    a.tiles_x = (uint32_t)((a.W / 4 + 63) / 64);
-    a.tiles_y = (uint32_t)((a.H + 4 * KM_SG_ROWS - 1) / (4 * KM_SG_ROWS));
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)a.BC;
-    KM_REQUIRE(nb < (1ull << 31), "km_spatial_gradient: grid too large");
-    a.nblocks = (uint32_t)nb;
+    if (km_set_grid(a, (a.W / 4 + 63) / 64, (a.H + 4 * KM_SG_ROWS - 1) / (4 * KM_SG_ROWS), (uint64_t)a.BC, "km_spatial_gradient")) return -1;
     if (a.kS == 3 && a.n_out == 2)
         hipLaunchKernelGGL((km_spatial_gradient_bwd_reg_kernel<T, 3, 2>), dim3(a.nblocks), dim3(256), 0, s, a);
     else if (a.kS == 3)
@@ -339,11 +323,7 @@ static bool km_sg_fast_ok(const void* x, const void* out, const void* mag, int H
 template <typename T>
 static int km_sg_fast_launch(const KmGradArgs<T>& a0, hipStream_t s) {
     KmGradArgs<T> a = a0;
-    a.tiles_x = (uint32_t)((a.W / 4 + 63) / 64);
-    a.tiles_y = (uint32_t)((a.H + 4 * KM_SG_ROWS - 1) / (4 * KM_SG_ROWS));
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)a.BC;
-    KM_REQUIRE(nb < (1ull << 31), "km_spatial_gradient: grid too large");
-    a.nblocks = (uint32_t)nb;
+    if (km_set_grid(a, (a.W / 4 + 63) / 64, (a.H + 4 * KM_SG_ROWS - 1) / (4 * KM_SG_ROWS), (uint64_t)a.BC, "km_spatial_gradient")) return -1;
     if (a.kS == 3 && a.n_out == 2)
         hipLaunchKernelGGL((km_spatial_gradient_reg_kernel<T, 3, 2>), dim3(a.nblocks), dim3(256), 0, s, a);
     else if (a.kS == 3)
@@ -364,12 +344,8 @@ static int km_grad_run(bool bwd, const void* x, const void* gout, const void* ke
     const R* kh = (const R*)kern_host;
     for (int t = 0; t < n_out * kS * kS; ++t) a.kern[t] = kh[t];
     a.eps = (R)eps; a.BC = BC; a.H = H; a.W = W; a.n_out = n_out; a.kS = kS;
-    a.tiles_x = (W + 63) / 64;
-    a.tiles_y = (H + 15) / 16;
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)BC;
-    KM_REQUIRE(nb < (1ull << 31), "km_spatial_gradient: grid too large");
-    a.nblocks = (uint32_t)nb;
-    if (nb == 0) return 0;
+    if (km_set_grid(a, (W + 63) / 64, (H + 15) / 16, (uint64_t)BC, "km_spatial_gradient")) return -1;
+    if (a.nblocks == 0) return 0;
     {
         const int generic = km_config().sg_generic;  // KM_SG_ALGO=generic: A/B timing
         if (!bwd && !generic && sizeof(T) != 8 && km_sg_fast_ok<T>(x, out, mag, H, W, n_out, kS)) return km_sg_fast_launch<T>(a, s);

@@ -67,11 +67,7 @@ __device__ __forceinline__ void kmm_median4(const float (&w)[5][8], float (&out)
 template <typename T, int K, bool IDX>
 __global__ __launch_bounds__(256) void km_median_reg_kernel(const KmMedArgs<T> a) {
     constexpr int PD = (K - 1) / 2, NV = 4 + 2 * PD;
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tbx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t tby = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tbx, tby, bc] = km_tile_of(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gx = (int)tbx * 64 + lane;               // column group (4 px)
     const int r0 = ((int)tby * 4 + wave) * KMM_ROWS;   // first output row of this wave's strip
@@ -292,11 +288,7 @@ static int kmm_fwd_fast(const void* x, void* y, void* idx, const void* apply, in
     KmMedArgs<T> a;
     a.x = (const T*)x; a.y = (T*)y; a.idx = (uint8_t*)idx; a.apply = (const float*)apply;
     a.C = C; a.H = H; a.W = W; a.ky = K; a.kx = K;
-    a.tiles_x = (uint32_t)((W / 4 + 63) / 64);
-    a.tiles_y = (uint32_t)((H + 4 * KMM_ROWS - 1) / (4 * KMM_ROWS));
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B * C;
-    KM_REQUIRE(nb < (1ull << 31), "km_median_blur_fwd: grid too large");
-    a.nblocks = (uint32_t)nb;
+    if (km_set_grid(a, (W / 4 + 63) / 64, (H + 4 * KMM_ROWS - 1) / (4 * KMM_ROWS), (uint64_t)B * C, "km_median_blur_fwd")) return -1;
     if (K == 3) {
         if (idx) hipLaunchKernelGGL((km_median_reg_kernel<T, 3, true>), dim3(a.nblocks), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((km_median_reg_kernel<T, 3, false>), dim3(a.nblocks), dim3(256), 0, s, a);
@@ -312,11 +304,7 @@ static int kmm_fwd_generic(const void* x, void* y, void* idx, const void* apply,
     KmMedArgs<T> a;
     a.x = (const T*)x; a.y = (T*)y; a.idx = (uint8_t*)idx; a.apply = (const float*)apply;
     a.C = C; a.H = H; a.W = W; a.ky = ky; a.kx = kx;
-    a.tiles_x = (uint32_t)((W + KMM_TW - 1) / KMM_TW);
-    a.tiles_y = (uint32_t)((H + KMM_TH - 1) / KMM_TH);
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B * C;
-    KM_REQUIRE(nb < (1ull << 31), "km_median_blur_fwd: grid too large");
-    a.nblocks = (uint32_t)nb;
+    if (km_set_grid(a, (W + KMM_TW - 1) / KMM_TW, (H + KMM_TH - 1) / KMM_TH, (uint64_t)B * C, "km_median_blur_fwd")) return -1;
     if (idx) hipLaunchKernelGGL((km_median_generic_kernel<T, true>), dim3(a.nblocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((km_median_generic_kernel<T, false>), dim3(a.nblocks), dim3(256), 0, s, a);
     return km_check_launch("km_median_blur_fwd(generic)");

@@ -26,14 +26,6 @@
 #include "km_regtile.h"
 #include "km_resize_axis.h"
 
-
-
-// value as the storage dtype would hold it
-__device__ __forceinline__ float kmp_round(float v, const float*) { return v; }
-__device__ __forceinline__ double kmp_round(double v, const double*) { return v; }
-__device__ __forceinline__ float kmp_round(float v, const km_bf16*) { return __uint_as_float(((uint32_t)km_f32_to_bf16_bits(v)) << 16); }
-__device__ __forceinline__ float kmp_round(float v, const km_f16*) { KM_OPAQUE(v); return (float)(km_f16)v; }
-
 template <typename T>
 struct KmPyrArgs {
     const T* x;
@@ -44,13 +36,10 @@ struct KmPyrArgs {
 
 template <typename T>
 __device__ __forceinline__ bool kmp_tile(const KmPyrArgs<T>& a, int& ox, int& oy, uint32_t& bc) {
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tbx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t tby = bid % a.tiles_y;
-    bc = bid / a.tiles_y;
-    ox = (int)tbx * 64 + (int)(threadIdx.x & 63);
-    oy = (int)tby * 4 + (int)(threadIdx.x >> 6);
+    const KmTile t = km_tile_of(a);
+    bc = t.bc;
+    ox = (int)t.tx * 64 + (int)(threadIdx.x & 63);
+    oy = (int)t.ty * 4 + (int)(threadIdx.x >> 6);
     return ox < a.ow && oy < a.oh;
 }
 
@@ -105,8 +94,8 @@ __global__ __launch_bounds__(256) void km_pyrdown_kernel(const KmPyrArgs<T> a) {
             s11 = km_fma(k, dy ? vc[p + 1][q] : vc[p][q], s11);
         }
     R blur[2][2];
-    blur[0][0] = kmp_round(s00, (const T*)nullptr); blur[0][1] = kmp_round(s01, (const T*)nullptr);
-    blur[1][0] = kmp_round(s10, (const T*)nullptr); blur[1][1] = kmp_round(s11, (const T*)nullptr);
+    blur[0][0] = km_round_as(s00, (const T*)nullptr); blur[0][1] = km_round_as(s01, (const T*)nullptr);
+    blur[1][0] = km_round_as(s10, (const T*)nullptr); blur[1][1] = km_round_as(s11, (const T*)nullptr);
     const R top = w0 * blur[0][0] + w1 * blur[0][1];
     const R bot = w0 * blur[1][0] + w1 * blur[1][1];
     km_st(a.y + ((size_t)bc * a.oh + oy) * a.ow + ox, h0 * top + h1 * bot);
@@ -149,11 +138,7 @@ __global__ __launch_bounds__(256) void km_resize_bilinear_kernel(const KmPyrArgs
 template <typename T>
 __global__ __launch_bounds__(256) void km_pyrdown2_kernel(const KmPyrArgs<T> a) {
     constexpr int K = 5, PD = 2, NV = 4 + 2 * PD;
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tbx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t tby = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tbx, tby, bc] = km_tile_of(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gx = (int)tbx * 64 + lane;              // column group (4 input px = 2 output px)
     const int r0 = ((int)tby * 4 + wave) * KMP_ROWS;  // first input row of this wave's strip (even)
@@ -208,7 +193,7 @@ __global__ __launch_bounds__(256) void km_pyrdown2_kernel(const KmPyrArgs<T> a) 
                         for (int p = 0; p < K; ++p)
 #pragma unroll
                             for (int q = 0; q < K; ++q) s = km_fma((taps[p] * taps[q]) / 256.f, ring[(kk + 1 + p) % K][c + q], s);
-                        cur[c] = kmp_round(s, (const T*)nullptr);
+                        cur[c] = km_round_as(s, (const T*)nullptr);
                     }
                     if (r & 1) {
                         // all four bilinear weights are exactly 1/2 here: h0*(w0*v00 + w1*v01) + h1*(w0*v10 + w1*v11)
@@ -233,11 +218,7 @@ __global__ __launch_bounds__(256) void km_pyrdown2_kernel(const KmPyrArgs<T> a) 
 template <typename T>
 __global__ __launch_bounds__(256) void km_pyrdown2_sep_kernel(const KmPyrArgs<T> a) {
     constexpr int K = 5, PD = 2, NV = 4 + 2 * PD;
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tbx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t tby = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tbx, tby, bc] = km_tile_of(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gx = (int)tbx * 64 + lane;
     const int r0 = ((int)tby * 4 + wave) * KMP_ROWS;
@@ -298,7 +279,7 @@ __global__ __launch_bounds__(256) void km_pyrdown2_sep_kernel(const KmPyrArgs<T>
                         float s = 0.f;
 #pragma unroll
                         for (int p = 0; p < K; ++p) s = km_fma(taps[p], ring[(kk + 1 + p) % K][c], s);
-                        cur[c] = kmp_round(s, (const T*)nullptr);
+                        cur[c] = km_round_as(s, (const T*)nullptr);
                     }
                     if (r & 1) {
                         const float o0 = 0.5f * (0.5f * prev[0] + 0.5f * prev[1]) + 0.5f * (0.5f * cur[0] + 0.5f * cur[1]);
@@ -325,11 +306,7 @@ __global__ __launch_bounds__(256) void km_pyrdown2_sep_kernel(const KmPyrArgs<T>
 template <typename T>
 __global__ __launch_bounds__(256) void km_resize2x_kernel(const KmPyrArgs<T> a) {
     typedef typename KmTraits<T>::R R;
-    uint32_t bid = km_xcd_remap(blockIdx.x, a.nblocks);
-    const uint32_t tbx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const uint32_t tby = bid % a.tiles_y;
-    const uint32_t bc = bid / a.tiles_y;
+    const auto [tbx, tby, bc] = km_tile_of(a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = (int)tbx * 64 + lane;               // source column pair
     const int s0 = ((int)tby * 4 + wave) * KMP_ROWS;  // first source row of this wave's strip
@@ -389,12 +366,8 @@ static int kmp_run_up2(const void* x, void* y, int B, int C, int H, int W, hipSt
     KmPyrArgs<T> a;
     a.x = (const T*)x; a.y = (T*)y;
     a.H = H; a.W = W; a.oh = 2 * H; a.ow = 2 * W; a.border = 0; a.align = 0;
-    a.tiles_x = (uint32_t)((W / 2 + 63) / 64);
-    a.tiles_y = (uint32_t)((H + 4 * KMP_ROWS - 1) / (4 * KMP_ROWS));
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B * (uint64_t)C;
-    KM_REQUIRE(nb < (1ull << 31), "km_resize_bilinear_fwd: grid too large");
-    a.nblocks = (uint32_t)nb;
-    if (nb == 0) return 0;
+    if (km_set_grid(a, (W / 2 + 63) / 64, (H + 4 * KMP_ROWS - 1) / (4 * KMP_ROWS), (uint64_t)B * C, "km_resize_bilinear_fwd")) return -1;
+    if (a.nblocks == 0) return 0;
     hipLaunchKernelGGL((km_resize2x_kernel<T>), dim3(a.nblocks), dim3(256), 0, s, a);
     return km_check_launch("km_resize_bilinear_fwd(x2)");
 }
@@ -411,12 +384,8 @@ static int kmp_run2(const void* x, void* y, int B, int C, int H, int W, int bord
     KmPyrArgs<T> a;
     a.x = (const T*)x; a.y = (T*)y;
     a.H = H; a.W = W; a.oh = H / 2; a.ow = W / 2; a.border = border; a.align = 0;
-    a.tiles_x = (uint32_t)((W / 4 + 63) / 64);
-    a.tiles_y = (uint32_t)((H + 4 * KMP_ROWS - 1) / (4 * KMP_ROWS));
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B * (uint64_t)C;
-    KM_REQUIRE(nb < (1ull << 31), "km_pyrdown_fwd: grid too large");
-    a.nblocks = (uint32_t)nb;
-    if (nb == 0) return 0;
+    if (km_set_grid(a, (W / 4 + 63) / 64, (H + 4 * KMP_ROWS - 1) / (4 * KMP_ROWS), (uint64_t)B * C, "km_pyrdown_fwd")) return -1;
+    if (a.nblocks == 0) return 0;
     if (km_config().pyrdown_separable) {  // KM_PYRDOWN_ALGO=separable: the 5 + 5 tap evaluation (A/B timing, see above)
         hipLaunchKernelGGL((km_pyrdown2_sep_kernel<T>), dim3(a.nblocks), dim3(256), 0, s, a);
         return km_check_launch("km_pyrdown_fwd(x2, separable)");
@@ -437,12 +406,8 @@ static int kmp_run(bool blur, const void* x, void* y, int B, int C, int H, int W
     KmPyrArgs<T> a;
     a.x = (const T*)x; a.y = (T*)y;
     a.H = H; a.W = W; a.oh = oh; a.ow = ow; a.border = border; a.align = align;
-    a.tiles_x = (uint32_t)((ow + 63) / 64);
-    a.tiles_y = (uint32_t)((oh + 3) / 4);
-    const uint64_t nb = (uint64_t)a.tiles_x * a.tiles_y * (uint64_t)B * (uint64_t)C;
-    KM_REQUIRE(nb < (1ull << 31), "km_pyramid: grid too large");
-    a.nblocks = (uint32_t)nb;
-    if (nb == 0) return 0;
+    if (km_set_grid(a, (ow + 63) / 64, (oh + 3) / 4, (uint64_t)B * C, "km_pyramid")) return -1;
+    if (a.nblocks == 0) return 0;
     if (blur) {
         hipLaunchKernelGGL((km_pyrdown_kernel<T>), dim3(a.nblocks), dim3(256), 0, s, a);
         return km_check_launch("km_pyrdown_fwd");

@@ -124,6 +124,271 @@ def test_warp_entry_points_host_contract_without_a_gpu():
             assert lib.km_warp2d_bwd_workspace_bytes(B, C, H, W, h, w, interp, pad, dtype) == want, (B, C, H, W, h, w, interp, pad, dtype)
 
 
+def test_filter_entry_points_host_contract_without_a_gpu():
+    """What the filter-family entry points (filter2d, separable, spatial gradient, pyramid, median, bilateral, canny) decide on the host,
+    before any launch: every argument check with its message (one defect per call), which message wins when a call has two defects, the
+    empty calls that return 0 with null pointers, every "grid too large" that int arguments reach without a launch, and the two
+    predicates as closed forms: the LDS budgets in the headers of km_filter.hip / km_filter_sep_big.hip, the window range of km_median.hip."""
+    from kornia_amd import _native
+
+    lib = _native.lib()
+    raw = ctypes.create_string_buffer(4096 + 32)
+    buf = (ctypes.addressof(raw) + 15) & ~15  # 16-byte aligned: the register-tiled paths take it
+    odd = buf + 4                               # element-aligned only: the generic paths
+    P = dict(constant=0, reflect=1, replicate=2, circular=3)
+
+    def rejected(rc, fragment, who=None):
+        msg = lib.km_last_error()
+        assert rc < 0 and fragment in msg and (who is None or msg.startswith(who + b":")), (rc, fragment, who, msg)
+
+    # ---- filter2d / filter2d_separable: the shared validation, then each entry point's own checks ----
+    def f2d(fn, ptrs=None, B=1, C=3, H=8, W=8, Bk=1, kH=3, kW=3, border=P["reflect"], same=1, dtype=0):
+        n_ptr = 4 if "sep" in fn else 3
+        ptrs = (buf,) * n_ptr if ptrs is None else ptrs
+        return getattr(lib, fn)(*ptrs, B, C, H, W, Bk, kH, kW, border, same, dtype, None)
+
+    for fn in ("km_filter2d_fwd", "km_filter2d_bwd_input", "km_filter2d_bwd_kernel", "km_filter2d_sep_fwd", "km_filter2d_sep_bwd_input"):
+        who, nulls = fn.encode(), (None,) * (4 if "sep" in fn else 3)
+        rejected(f2d(fn, H=0), b"bad shape B=1 C=3 H=0 W=8", who)
+        rejected(f2d(fn, B=-1), b"bad shape B=-1", who)
+        rejected(f2d(fn, H=65536, W=32768), b"image plane exceeds 2^31 elements", who)
+        rejected(f2d(fn, kH=0), b"bad kernel size 0x3", who)
+        rejected(f2d(fn, B=2, Bk=3), b"kernel batch 3 must divide the input batch 2", who)
+        rejected(f2d(fn, Bk=0), b"kernel batch 0 must divide", who)
+        rejected(f2d(fn, border=4), b"bad border 4", who)
+        rejected(f2d(fn, dtype=4), b"bad dtype 4", who)
+        rejected(f2d(fn, dtype=-1), b"bad dtype -1", who)
+        rejected(f2d(fn, H=2, kH=5), b"reflect padding must be smaller than the image", who)  # pad 2 >= H
+        rejected(f2d(fn, W=2, kW=6, border=P["circular"]), b"circular padding must not exceed the image", who)  # rear pad 3 > W
+        rejected(f2d(fn, kH=9, same=0), b"'valid' needs kernel <= image", who)
+        rejected(f2d(fn, ptrs=nulls), b"null pointer", who)
+        for i in range(len(nulls)):
+            rejected(f2d(fn, ptrs=tuple(None if j == i else buf for j in range(len(nulls)))), b"null pointer", who)
+        # two defects: the checks run in the order above (shape, plane, kernel, batch, border, dtype, pad, pointers)
+        rejected(f2d(fn, H=0, kH=0), b"bad shape", who)
+        rejected(f2d(fn, border=4, dtype=4), b"bad border 4", who)
+        rejected(f2d(fn, ptrs=nulls, dtype=4), b"bad dtype 4", who)
+        # empty batch: nothing is looked at
+        assert f2d(fn, ptrs=nulls, B=0) == 0 and f2d(fn, ptrs=nulls, C=0) == 0
+        assert f2d(fn, ptrs=nulls, B=0, H=0, kH=0, border=9, dtype=9) == 0
+
+    rejected(f2d("km_filter2d_bwd_input", kH=130, border=P["constant"]), b"km_filter2d_bwd_input: kernel too large")  # rear pad 65 >= 64 pre-images
+    rejected(f2d("km_filter2d_bwd_input", kW=130, border=P["constant"]), b"km_filter2d_bwd_input: kernel too large")
+    rejected(f2d("km_filter2d_bwd_input", ptrs=(None,) * 3, kH=130, border=P["constant"]), b"null pointer")
+    rejected(f2d("km_filter2d_bwd_kernel", kH=256, kW=256, border=P["constant"]), b"km_filter2d_bwd_kernel: kernel too large")
+    rejected(f2d("km_filter2d_sep_bwd_input", kH=34, border=P["constant"]), b"km_filter2d_sep_bwd_input: kernel larger than the tile; use the generic path")
+    rejected(f2d("km_filter2d_sep_bwd_input", kW=66, border=P["constant"]), b"kernel larger than the tile")
+    rejected(f2d("km_filter2d_sep_bwd_input", ptrs=(None,) * 4, kH=34, border=P["constant"]), b"null pointer")
+    rejected(f2d("km_filter2d_sep_fwd", kH=99, border=P["constant"]), b"km_filter2d_sep: kernel 99x3 needs 68008 B of LDS (> 65536); use the two-pass generic path")
+    rejected(f2d("km_filter2d_sep_bwd_input", kH=33, kW=33, border=P["constant"]), b"km_filter2d_sep: kernel 33x33 needs 143624 B of LDS (> 65536)")
+
+    # "grid too large": 2^31 planes of one tile each (B C = 65536 x 32768); the aligned buffer reaches the register-tiled launchers, the
+    # element-aligned one, fp64 and the kernel sizes beyond them the generic ones
+    big = dict(B=65536, C=32768)
+    for ptrs in ((buf,) * 3, (odd,) * 3):
+        rejected(f2d("km_filter2d_fwd", ptrs=ptrs, **big), b"km_filter2d: grid too large")
+        rejected(f2d("km_filter2d_bwd_input", ptrs=ptrs, **big), b"km_filter2d: grid too large")
+    rejected(f2d("km_filter2d_fwd", kH=4, kW=4, **big), b"km_filter2d: grid too large")
+    rejected(f2d("km_filter2d_bwd_input", H=4, **big), b"km_filter2d: grid too large")  # H <= 2 pd: no frame pass, the generic adjoint
+    rejected(f2d("km_filter2d_bwd_kernel", **big), b"km_filter2d_bwd_kernel: grid too large")
+    for fn in ("km_filter2d_sep_fwd", "km_filter2d_sep_bwd_input"):
+        rejected(f2d(fn, **big), b"km_blur: grid too large")
+        rejected(f2d(fn, ptrs=(odd,) * 4, **big), b"km_filter2d_sep: grid too large")
+        rejected(f2d(fn, dtype=1, **big), b"km_filter2d_sep: grid too large")
+    rejected(f2d("km_filter2d_sep_fwd", kH=23, kW=23, border=P["constant"], **big), b"km_filter2d_sep: grid too large")  # the big-kernel forward
+
+    # ---- km_filter2d_sep_supported: the LDS budgets of km_filter.hip (64 x 32 tile) and km_filter_sep_big.hip (64 x 64 tile) ----
+    def sep_supported(kH, kW, same, dtype):
+        elem = 8 if dtype == 1 else 4  # compute type: fp64 for f64 data, fp32 otherwise
+        mask = 0
+        pitch = (64 + kW - 1 + 8 + 3) // 4 * 4
+        if dtype != 1 and (kH >= 10 or kW >= 10) and pitch <= 128 and ((64 + kH - 1) * pitch + (64 + kH - 1) * 64) * 4 <= 65536:
+            mask |= 1
+        if kH - 1 > 32 or kW - 1 > 64:
+            return mask
+        IW, IH = 64 + kW - 1, 32 + kH - 1
+        if (IH * IW + IH * 64 + kW + kH) * elem <= 65536:
+            mask |= 1
+        lt = (kH - 1) // 2 if same else 0
+        rb = kH - 1 - lt if same else 0
+        ll = (kW - 1) // 2 if same else 0
+        rr = kW - 1 - ll if same else 0
+        EH, UW, EW, VH = 32 + lt + 2 * rb, 64 + (kW - 1) + ll + 2 * rr, 64 + ll + 2 * rr, 32 + (kH - 1) + lt + 2 * rb
+        if (VH * UW + EH * UW + 32 * UW + 32 * EW + kW + kH) * elem <= 65536:
+            mask |= 2
+        return mask
+
+    sizes = (1, 2, 3, 5, 9, 10, 11, 23, 33, 34, 65, 66, 99)
+    seen = set()
+    for kH in sizes:
+        for kW in sizes:
+            for same in (0, 1):
+                for dtype in range(4):
+                    want = sep_supported(kH, kW, same, dtype)
+                    assert lib.km_filter2d_sep_supported(kH, kW, same, dtype) == want, (kH, kW, same, dtype, want)
+                    seen.add(want)
+    assert seen == {0, 1, 3}  # (the adjoint's tile never fits where the forward's does not)
+
+    # ---- spatial gradient ----
+    def sg(fn="fwd", x=buf, kern=buf, out=buf, mag=None, B=1, C=3, H=8, W=8, n_out=2, kS=3, dtype=0):
+        if fn == "fwd":
+            return lib.km_spatial_gradient_fwd(x, kern, out, mag, B, C, H, W, n_out, kS, 0.0, dtype, None)
+        return lib.km_spatial_gradient_bwd(x, kern, out, B, C, H, W, n_out, kS, dtype, None)
+
+    for fn in ("fwd", "bwd"):
+        who = b"km_spatial_gradient_" + fn.encode()
+        rejected(sg(fn, W=0), b"bad shape", who)
+        rejected(sg(fn, H=65536, W=32768), b"image plane exceeds 2^31 elements", who)
+        rejected(sg(fn, n_out=4), b"n_out must be 1..3, got 4", who)
+        rejected(sg(fn, n_out=0), b"n_out must be 1..3, got 0", who)
+        rejected(sg(fn, kS=7), b"kernel size must be odd and <= 5, got 7", who)
+        rejected(sg(fn, kS=2), b"kernel size must be odd and <= 5, got 2", who)
+        rejected(sg(fn, dtype=4), b"bad dtype", who)
+        rejected(sg(fn, x=None), b"null pointer", who)
+        rejected(sg(fn, kern=None), b"null pointer", who)
+        rejected(sg(fn, out=None), b"null pointer", who)
+        rejected(sg(fn, W=0, n_out=4), b"bad shape", who)
+        rejected(sg(fn, x=None, dtype=4), b"bad dtype", who)
+        assert sg(fn, x=None, kern=None, out=None, B=0) == 0 and sg(fn, x=None, kern=None, out=None, C=0, W=0, kS=9) == 0
+        for n_out, kS in ((1, 3), (2, 3), (3, 5)):
+            rejected(sg(fn, B=65536, C=16384, H=17, n_out=n_out, kS=kS), b"km_spatial_gradient: grid too large")
+    rejected(sg(out=None, mag=buf, n_out=3), b"km_spatial_gradient_fwd: magnitude needs n_out == 2")
+    rejected(sg(x=None, out=None, mag=buf, n_out=3), b"null pointer")
+
+    # ---- pyramid: pyrdown, bilinear resize and its adjoint ----
+    def pyr(fn, x=buf, y=buf, B=1, C=3, H=8, W=8, oh=4, ow=4, border=P["reflect"], align=0, dtype=0):
+        if fn == "km_pyrdown_fwd":
+            return lib.km_pyrdown_fwd(x, y, B, C, H, W, oh, ow, border, align, dtype, None)
+        return getattr(lib, fn)(x, y, B, C, H, W, oh, ow, align, dtype, None)
+
+    for fn in ("km_pyrdown_fwd", "km_resize_bilinear_fwd"):
+        who = fn.encode()
+        rejected(pyr(fn, H=0), b"bad shape B=1 C=3 H=0 W=8 -> 4x4", who)
+        rejected(pyr(fn, oh=-1), b"bad shape", who)
+        rejected(pyr(fn, dtype=4), b"unknown dtype code 4", who)
+        rejected(pyr(fn, x=None), b"null pointer", who)
+        rejected(pyr(fn, y=None), b"null pointer", who)
+        rejected(pyr(fn, H=0, dtype=4), b"bad shape", who)
+        rejected(pyr(fn, x=None, dtype=4), b"unknown dtype code 4", who)
+        for empty in (dict(B=0), dict(C=0), dict(oh=0), dict(ow=0)):
+            assert pyr(fn, x=None, y=None, **empty) == 0
+        rejected(pyr(fn, x=None, y=None, oh=0, dtype=4), b"unknown dtype code 4", who)  # (an empty output is still validated)
+        rejected(pyr(fn, align=1, **big), b"km_pyramid: grid too large")
+    rejected(pyr("km_pyrdown_fwd", border=4), b"km_pyrdown_fwd: unknown border code 4")
+    rejected(pyr("km_pyrdown_fwd", H=2), b"km_pyrdown_fwd: reflect padding needs H, W > 2 (got 2x8)")
+    rejected(pyr("km_pyrdown_fwd", x=None, border=4), b"null pointer")
+    rejected(pyr("km_pyrdown_fwd", oh=0, border=4), b"unknown border code 4")
+    rejected(pyr("km_pyrdown_fwd", **big), b"km_pyrdown_fwd: grid too large")               # the factor-2 kernel
+    rejected(pyr("km_resize_bilinear_fwd", oh=16, ow=16, **big), b"km_resize_bilinear_fwd: grid too large")  # the x2 kernel
+    who = b"km_resize_bilinear_bwd"
+    rejected(pyr("km_resize_bilinear_bwd", oh=0), b"bad shape B=1 C=3 H=8 W=8 <- 0x4", who)
+    rejected(pyr("km_resize_bilinear_bwd", W=0), b"bad shape", who)
+    rejected(pyr("km_resize_bilinear_bwd", dtype=4), b"unknown dtype code 4", who)
+    rejected(pyr("km_resize_bilinear_bwd", x=None), b"null pointer", who)
+    rejected(pyr("km_resize_bilinear_bwd", y=None), b"null pointer", who)
+    rejected(pyr("km_resize_bilinear_bwd", W=0, dtype=4), b"bad shape", who)
+    assert pyr("km_resize_bilinear_bwd", x=None, y=None, B=0) == 0 and pyr("km_resize_bilinear_bwd", x=None, y=None, C=0) == 0
+    rejected(pyr("km_resize_bilinear_bwd", B=1, C=1, H=1 << 20, W=1 << 20), b"km_resize_bilinear_bwd: grid too large")  # block rows
+    rejected(pyr("km_resize_bilinear_bwd", B=65536, C=65536), b"km_resize_bilinear_bwd: grid too large")              # planes
+
+    # ---- median ----
+    def med(fn="fwd", ptrs=None, B=1, C=3, H=8, W=8, ky=3, kx=3, dtype=0):
+        if fn == "fwd":
+            x, y, idx, apply = (buf, buf, buf, None) if ptrs is None else ptrs
+            return lib.km_median_blur_fwd(x, y, idx, apply, B, C, H, W, ky, kx, dtype, None)
+        gy, idx, apply, gx = (buf, buf, None, buf) if ptrs is None else ptrs
+        return lib.km_median_blur_bwd(gy, idx, apply, gx, B, C, H, W, ky, kx, dtype, None)
+
+    for fn in ("fwd", "bwd"):
+        who = b"km_median_blur_" + fn.encode()
+        rejected(med(fn, ky=4), b"the window must have odd sides of 1 .. 15, got (4, 3)", who)
+        rejected(med(fn, kx=17), b"the window must have odd sides of 1 .. 15, got (3, 17)", who)
+        rejected(med(fn, ky=0), b"the window must have odd sides", who)
+        rejected(med(fn, dtype=4), b"bad dtype 4", who)
+        rejected(med(fn, B=-1), b"bad shape B=-1 C=3 H=8 W=8", who)
+        rejected(med(fn, H=65536, W=32768), b"bad shape", who)
+        rejected(med(fn, ptrs=(None,) * 4), b"null pointer", who)
+        rejected(med(fn, ky=4, dtype=4), b"the window must have odd sides", who)
+        rejected(med(fn, B=-1, dtype=4), b"bad dtype 4", who)
+        for empty in (dict(B=0), dict(C=0), dict(H=0), dict(W=0)):
+            assert med(fn, ptrs=(None,) * 4, **empty) == 0
+        rejected(med(fn, ptrs=(None,) * 4, H=0, ky=4), b"the window must have odd sides", who)
+    rejected(med(ptrs=(None, buf, buf, None)), b"null pointer")
+    rejected(med(ptrs=(buf, None, buf, None)), b"null pointer")
+    rejected(med("bwd", ptrs=(None, buf, None, buf)), b"null pointer")
+    rejected(med("bwd", ptrs=(buf, None, None, buf)), b"null pointer")
+    rejected(med("bwd", ptrs=(buf, buf, None, None)), b"null pointer")
+    rejected(med(**big), b"km_median_blur_fwd: grid too large")                                   # register-tiled 3 x 3
+    rejected(med(ptrs=(odd, odd, odd, None), **big), b"km_median_blur_fwd: grid too large")       # generic
+    rejected(med(ky=7, kx=7, **big), b"km_median_blur_fwd: grid too large")
+    rejected(med("bwd", H=16, W=16, **big), b"km_median_blur_bwd: grid too large")                # 2^39 pixels, 256 per block
+    for ky in range(-1, 19):
+        for kx in range(-1, 19):
+            for dtype in range(-1, 6):
+                want = 1 if (1 <= ky <= 15 and 1 <= kx <= 15 and ky % 2 == 1 and kx % 2 == 1 and 0 <= dtype <= 3) else 0
+                assert lib.km_median_blur_supported(ky, kx, dtype) == want, (ky, kx, dtype)
+
+    # ---- bilateral ----
+    def bil(fn="fwd", ptrs=None, guide=None, B=1, C=3, Cg=0, H=8, W=8, Bs=1, Bc=1, ky=3, kx=3, border=P["reflect"], dist=0, dtype=0):
+        if fn == "fwd":
+            x, space, coef, y, wsum = (buf, buf, buf, buf, buf) if ptrs is None else ptrs
+            return lib.km_bilateral_blur_fwd(x, guide, space, coef, y, wsum, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, dtype, None)
+        x, space, coef, y, wsum, gy, gx, gg = (buf, buf, buf, buf, buf, buf, buf, None) if ptrs is None else ptrs
+        return lib.km_bilateral_blur_bwd(x, guide, space, coef, y, wsum, gy, gx, gg, B, C, Cg, H, W, Bs, Bc, ky, kx, border, dist, dtype, None)
+
+    for fn, n_ptr in (("fwd", 5), ("bwd", 8)):
+        who = b"km_bilateral_blur_" + fn.encode()
+        rejected(bil(fn, ky=4), b"the window must have odd sides of 1 .. 15, got (4, 3)", who)
+        rejected(bil(fn, kx=17), b"the window must have odd sides of 1 .. 15, got (3, 17)", who)
+        rejected(bil(fn, dtype=4), b"bad dtype 4", who)
+        rejected(bil(fn, border=4), b"bad border code 4", who)
+        rejected(bil(fn, dist=2), b"bad distance code 2", who)
+        rejected(bil(fn, H=-1), b"bad shape B=1 C=3 H=-1 W=8", who)
+        rejected(bil(fn, H=65536, W=32768), b"bad shape", who)
+        rejected(bil(fn, C=17), b"at most 16 channels of input and of guidance, got 17 and 17", who)
+        rejected(bil(fn, guide=buf, Cg=0), b"at most 16 channels of input and of guidance, got 3 and 0", who)
+        rejected(bil(fn, guide=buf, Cg=17), b"at most 16 channels of input and of guidance, got 3 and 17", who)
+        rejected(bil(fn, B=4, Bs=2), b"space has 2 and coef 1 samples, each must be 1 or B=4", who)
+        rejected(bil(fn, B=4, Bc=3), b"space has 1 and coef 3 samples, each must be 1 or B=4", who)
+        rejected(bil(fn, H=2, ky=5), b"a reflect pad of (2, 1) does not fit the 2 x 8 image", who)
+        rejected(bil(fn, W=2, kx=7, border=P["circular"]), b"a circular pad of (1, 3) wraps the 8 x 2 image more than once", who)
+        rejected(bil(fn, ptrs=(None,) * n_ptr), b"null pointer", who)
+        rejected(bil(fn, ky=4, dtype=4), b"the window must have odd sides", who)
+        rejected(bil(fn, ptrs=(None,) * n_ptr, H=2, ky=5), b"a reflect pad", who)
+        for empty in (dict(B=0), dict(C=0), dict(H=0), dict(W=0)):
+            assert bil(fn, ptrs=(None,) * n_ptr, **empty) == 0
+        rejected(bil(fn, ptrs=(None,) * n_ptr, H=0, dist=2), b"bad distance code 2", who)  # (an empty call is still validated)
+        assert bil(fn, ptrs=(None,) * n_ptr, H=0, ky=5) == 0                                # ... but its pad is not
+        rejected(bil(fn, B=1 << 30, C=1, H=9), b"km_bilateral_blur_" + fn.encode() + b": grid too large")  # two 32 x 8 tiles a sample
+    for i in (0, 1, 2, 3):  # x, space, coef, y; wsum is optional in the forward
+        rejected(bil(ptrs=tuple(None if j == i else buf for j in range(5))), b"null pointer")
+    for i in (0, 1, 2, 3, 4, 5):
+        rejected(bil("bwd", ptrs=tuple(None if j == i else (None if j == 7 else buf) for j in range(8))), b"null pointer")
+    rejected(bil("bwd", ptrs=(buf,) * 6 + (None, None)), b"km_bilateral_blur_bwd: self-guided takes gx alone, joint at least one of gx and gguide")
+    rejected(bil("bwd", ptrs=(buf,) * 8), b"self-guided takes gx alone")
+    rejected(bil("bwd", guide=buf, Cg=1, ptrs=(buf,) * 6 + (None, None)), b"joint at least one of gx and gguide")
+    rejected(bil(B=1 << 30, C=16, H=9, ky=15, kx=15, dtype=1), b"km_bilateral_blur_fwd: grid too large")  # the run-time forward, its tile shrunk
+
+    # ---- canny ----
+    def nms(ptrs=(buf, buf, buf), B=1, H=8, W=8):
+        return lib.km_canny_nms_fwd(*ptrs, B, H, W, 0.1, 0.2, 1e-6, None)
+
+    def hyst(ptrs=(buf, buf, buf), B=1, H=8, W=8):
+        return lib.km_canny_hysteresis_sweep(*ptrs, B, H, W, None)
+
+    for call, who in ((nms, b"km_canny_nms_fwd"), (hyst, b"km_canny_hysteresis_sweep")):
+        for i in range(3):
+            rejected(call(ptrs=tuple(None if j == i else buf for j in range(3))), b"null pointer", who)
+        rejected(call(B=-1), b"bad shape", who)
+        rejected(call(H=-1), b"bad shape", who)
+        rejected(call(ptrs=(None,) * 3, W=-1), b"null pointer", who)
+        for empty in (dict(B=0), dict(H=0), dict(W=0)):
+            assert call(ptrs=(None,) * 3, **empty) == 0
+        assert call(ptrs=(None,) * 3, B=0, H=-1) == 0
+    rejected(nms(B=2, H=1 << 20, W=1 << 20), b"km_canny_nms_fwd: grid too large")              # 64 x 16 tiles
+    rejected(hyst(B=2, H=1 << 21, W=1 << 21), b"km_canny_hysteresis_sweep: grid too large")  # 64 x 64 tiles
+
+
 def test_launch_contract():
     """_native.launch(name, device, *args): the entry point gets (*args, stream_ptr(device)) under exactly one device_guard(device); 0 returns
     None without asking for the error text, anything else raises NativeLibraryError with the name, the code and km_last_error().  `lib`,
