@@ -65,12 +65,13 @@ int km_device_info(char* name, int n);
  * every launch forward (what a per-kernel timing loop over one input needs: otherwise launch k+1 re-reads the tail launch k just
  * read).  Results do not depend on it.  Returns the previous mode.  (No reference counterpart: the reference has no launch policy.) */
 int km_set_traversal(int mode);
-/* Launch policy.  The library reads its A/B switches (profiles/README.md: KM_WARP_FWD_ALGO, KM_BLUR_ROWS, ...) from the environment ONCE,
- * when it is first used; no launcher calls getenv.  km_config_set changes one entry explicitly ("traversal_fixed", "warp_fwd_algo",
- * "warp_gm_algo", "warp_bwd_generic", "warp_bwd_fused", "sep_lds", "sg_generic", "pyrdown_separable", "blur_rows", "warp_bwd_no_scan", "pair_fused") and returns its
- * previous value (-1: unknown key).  For tests and A/B timing - call it between launches, not concurrently with them.  The alternating
- * traversal itself keeps its parity per (device, stream): what one stream launches never changes the order another stream's kernels
- * walk the batch.  (No reference counterpart.) */
+/* Launch policy.  The library reads its A/B switches from the environment ONCE, when it is first used; no launcher calls getenv.  The one
+ * list of them - key, environment variable, spellings, values, defaults - is the table g_km_switches in kornia_amd/csrc/km_runtime.hip.
+ * km_config_set changes one entry explicitly and returns its previous value, km_config_get returns the current one (-1 and a message in
+ * km_last_error: unknown key).  Keys: "traversal_fixed", "warp_fwd_algo", "warp_gm_algo", "warp_bwd_generic", "warp_bwd_fused", "sep_lds",
+ * "sg_generic", "blur_rows", "warp_bwd_no_scan", "pair_fused".  For tests and A/B timing - call it between launches, not concurrently with
+ * them.  The alternating traversal itself keeps its parity per (device, stream): what one stream launches never changes the order another
+ * stream's kernels walk the batch.  (No reference counterpart.) */
 int km_config_set(const char* key, int value);
 int km_config_get(const char* key);
 /* Diagnostic: a plain streaming copy of `bytes` bytes (a multiple of 16, both pointers 16-byte aligned), 16 bytes per lane, nontemporal != 0:

@@ -414,23 +414,18 @@ __device__ __forceinline__ int km_tid_pinned() {
 // The parity is per (device, stream); KM_TRAVERSAL=fixed / km_set_traversal(1) keeps every launch forward (A/B).
 uint32_t km_traversal_next(hipStream_t s);
 
-#ifndef KM_PAIR_FUSED_DEFAULT
-#define KM_PAIR_FUSED_DEFAULT 2  // km_warp2d_pair_fwd: 1 one launch (km_warp_pair_kernel), 0 two launches, 2 one launch for perspective / two for affine
-                                 // (what measured faster on each: profiles/README.md, r07)
-#endif
-// Launch policy, read once from the environment when the library is first used (km_runtime.hip); see profiles/README.md
+// Launch policy: what the launchers read.  Keys, environment variables, values and defaults: the table g_km_switches in km_runtime.hip.
 struct KmConfig {
-    int traversal_fixed;    // KM_TRAVERSAL=fixed
-    int warp_fwd_algo;      // KM_WARP_FWD_ALGO: 0 default, 1 generic, 3 box (km_warp_fwd_box_kernel), 4 rows (the gather kernel)
-    int warp_gm_algo;       // KM_WARP_GM_ALGO: 0 default (box form where it applies), 1 generic, 2 lds, 3 rows (the gather kernel)
-    int warp_bwd_generic;   // KM_WARP_BWD_ALGO=generic
-    int warp_bwd_fused;     // KM_WARP_BWD_FUSED=0 turns the one-read backward off (two launches)
-    int sep_lds;            // KM_SEP_ALGO=lds
-    int sg_generic;         // KM_SG_ALGO=generic
-    int pyrdown_separable;  // KM_PYRDOWN_ALGO=separable
-    int blur_rows;          // KM_BLUR_ROWS=8 / 16 / 32 (0: by storage type, direction, kernel size and size of the launch: km_blur_rows)
-    int pair_fused;         // KM_PAIR_ALGO=fused / two: km_warp2d_pair_fwd as one launch (image + first mask) or two; default KM_PAIR_FUSED_DEFAULT
-    int warp_bwd_no_scan;   // KM_WARP_BWD_SCAN=0: the one-read backward does not look for non-finite gradients at output pixels that sample entirely outside the source
+    int traversal_fixed;   // != 0: every launch forward
+    int warp_fwd_algo;     // 0 default, 1 generic, 3 box, 4 rows
+    int warp_gm_algo;      // 0 default, 1 generic, otherwise the gather kernel
+    int warp_bwd_generic;  // != 0
+    int warp_bwd_fused;    // != 0: the one-read backward where it applies
+    int sep_lds;           // != 0
+    int sg_generic;        // != 0
+    int blur_rows;         // 8 / 16 / 32, 0: km_blur_rows
+    int pair_fused;        // 1 one launch, 0 two, 2 by coordinate generator
+    int warp_bwd_no_scan;  // != 0
 };
 const KmConfig& km_config();
 int km_device_cus();

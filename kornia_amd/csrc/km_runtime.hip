@@ -20,34 +20,48 @@ void km_set_error(const char* fmt, ...) {
 }
 
 // ---- launch policy ---------------------------------------------------------------------------------------------------------------
-// Read ONCE, when the library is first used (the A/B switches of profiles/README.md); launchers read the struct, never the
-// environment.  km_config_set changes an entry explicitly (tests, A/B timing of one process) - it is not meant to race with launches.
+// THE list of the A/B switches: one row per entry of KmConfig - the key km_config_set / km_config_get take, the member, the environment
+// variable and how its value is decoded (only the FIRST CHARACTER of a spelling is looked at; v == nullptr: the variable is not set).
+// The environment is read ONCE, when the library is first used; launchers read the struct, never the environment.  km_config_set
+// changes an entry explicitly (tests, A/B timing of one process) - it is not meant to race with launches - and stores any int: an
+// entry that its launcher tests against listed values treats the others as the comment of its decoder says.
+// km_warp2d_pair_fwd without KM_PAIR_ALGO: 1 one launch (km_warp_pair_kernel), 0 two launches, 2 one launch for perspective / two for
+// affine (what measured faster on each: profiles/README.md, r07)
+static const int KM_PAIR_FUSED_DEFAULT = 2;
+template <char C>
+static int km_dec_is(const char* v) { return v && v[0] == C; }  // 1 for the spelling that starts with C, 0 otherwise and when unset
+static int km_dec_warp_fwd(const char* v) {  // generic -> 1, box -> 3 (km_warp_fwd_box_kernel), rows -> 4 (the gather kernel); 0: by the launcher's own rules
+    return !v ? 0 : (v[0] == 'g' ? 1 : (v[0] == 'b' ? 3 : (v[0] == 'r' ? 4 : 0)));
+}
+static int km_dec_warp_gm(const char* v) {  // generic -> 1 (inside the atomic-scatter kernel), rows -> 3 (the gather kernel where the box form would run);
+    return !v ? 0 : (v[0] == 'g' ? 1 : (v[0] == 'r' ? 3 : 0));  // 0: the box form where it applies.  Any other non-zero value set by key acts like 3.
+}
+static int km_dec_not_0(const char* v) { return km_dec_is<'0'>(v) ? 0 : 1; }  // on unless the value starts with 0
+static int km_dec_int(const char* v) { return v ? atoi(v) : 0; }
+static int km_dec_pair(const char* v) {  // fused -> 1, two -> 0
+    return !v ? KM_PAIR_FUSED_DEFAULT : (v[0] == 'f' ? 1 : (v[0] == 't' ? 0 : KM_PAIR_FUSED_DEFAULT));
+}
+static const struct KmSwitch {
+    const char* key;
+    int KmConfig::*field;
+    const char* env;
+    int (*decode)(const char* v);
+} g_km_switches[] = {
+    {"traversal_fixed", &KmConfig::traversal_fixed, "KM_TRAVERSAL", km_dec_is<'f'>},          // =fixed: every launch walks the batch forward (km_traversal_next)
+    {"warp_fwd_algo", &KmConfig::warp_fwd_algo, "KM_WARP_FWD_ALGO", km_dec_warp_fwd},
+    {"warp_gm_algo", &KmConfig::warp_gm_algo, "KM_WARP_GM_ALGO", km_dec_warp_gm},
+    {"warp_bwd_generic", &KmConfig::warp_bwd_generic, "KM_WARP_BWD_ALGO", km_dec_is<'g'>},    // =generic: the atomic-scatter backward
+    {"warp_bwd_fused", &KmConfig::warp_bwd_fused, "KM_WARP_BWD_FUSED", km_dec_not_0},         // =0: the one-read backward off (two launches)
+    {"sep_lds", &KmConfig::sep_lds, "KM_SEP_ALGO", km_dec_is<'l'>},                           // =lds: the generic and LDS-tiled filter kernels where a register-tiled one would run
+    {"sg_generic", &KmConfig::sg_generic, "KM_SG_ALGO", km_dec_is<'g'>},                      // =generic: the generic spatial-gradient kernel
+    {"blur_rows", &KmConfig::blur_rows, "KM_BLUR_ROWS", km_dec_int},                          // =8 / 16 / 32 rows per strip; 0: km_blur_rows chooses
+    {"warp_bwd_no_scan", &KmConfig::warp_bwd_no_scan, "KM_WARP_BWD_SCAN", km_dec_is<'0'>},    // =0: no scan for non-finite gradients at pixels that sample outside the source
+    {"pair_fused", &KmConfig::pair_fused, "KM_PAIR_ALGO", km_dec_pair},
+};
 static KmConfig g_km_config;
 static std::once_flag g_km_config_once;
-static int km_env_first(const char* name, char c0, char c1 = 0) {
-    const char* e = getenv(name);
-    if (!e) return 0;
-    if (e[0] == c0) return 1;
-    if (c1 && e[0] == c1) return 2;
-    return 0;
-}
 static void km_config_init() {
-    KmConfig& c = g_km_config;
-    c.traversal_fixed = km_env_first("KM_TRAVERSAL", 'f');
-    c.warp_fwd_algo = km_env_first("KM_WARP_FWD_ALGO", 'g');        // 1 generic, 3 box, 4 rows (the gather kernel)
-    if (!c.warp_fwd_algo) c.warp_fwd_algo = km_env_first("KM_WARP_FWD_ALGO", 'b') ? 3 : (km_env_first("KM_WARP_FWD_ALGO", 'r') ? 4 : 0);
-    c.warp_gm_algo = km_env_first("KM_WARP_GM_ALGO", 'g', 'l');     // 1 generic, 2 lds, 3 rows (the gather kernel where the box form would run)
-    if (!c.warp_gm_algo && km_env_first("KM_WARP_GM_ALGO", 'r')) c.warp_gm_algo = 3;
-    c.warp_bwd_generic = km_env_first("KM_WARP_BWD_ALGO", 'g');
-    c.warp_bwd_fused = km_env_first("KM_WARP_BWD_FUSED", '0') ? 0 : 1;
-    c.sep_lds = km_env_first("KM_SEP_ALGO", 'l');
-    c.sg_generic = km_env_first("KM_SG_ALGO", 'g');
-    c.pyrdown_separable = km_env_first("KM_PYRDOWN_ALGO", 's');
-    const char* br = getenv("KM_BLUR_ROWS");
-    c.blur_rows = br ? atoi(br) : 0;
-    c.warp_bwd_no_scan = km_env_first("KM_WARP_BWD_SCAN", '0');
-    c.pair_fused = km_env_first("KM_PAIR_ALGO", 'f', 't');
-    c.pair_fused = c.pair_fused == 1 ? 1 : (c.pair_fused == 2 ? 0 : KM_PAIR_FUSED_DEFAULT);  // (f: 1, t: 0, unset: the default)
+    for (const KmSwitch& sw : g_km_switches) g_km_config.*sw.field = sw.decode(getenv(sw.env));
 }
 const KmConfig& km_config() {
     std::call_once(g_km_config_once, km_config_init);
@@ -191,20 +205,12 @@ int km_set_traversal(int mode) {
     return prev;
 }
 
-// Explicit setter of a launch-policy entry (the names of KmConfig's fields); returns the previous value, -1 for an unknown key.
+// Explicit setter of a launch-policy entry (the keys of g_km_switches); returns the previous value, -1 for an unknown key.
 // For tests and A/B timing: call it between launches, not concurrently with them.
 static int* km_config_field(const char* key) {
-    struct { const char* name; int* field; } table[] = {
-        {"traversal_fixed", &g_km_config.traversal_fixed}, {"warp_fwd_algo", &g_km_config.warp_fwd_algo},
-        {"warp_gm_algo", &g_km_config.warp_gm_algo},       {"warp_bwd_generic", &g_km_config.warp_bwd_generic},
-        {"warp_bwd_fused", &g_km_config.warp_bwd_fused},   {"sep_lds", &g_km_config.sep_lds},
-        {"sg_generic", &g_km_config.sg_generic},           {"pyrdown_separable", &g_km_config.pyrdown_separable},
-        {"blur_rows", &g_km_config.blur_rows},                 {"warp_bwd_no_scan", &g_km_config.warp_bwd_no_scan},
-        {"pair_fused", &g_km_config.pair_fused},
-    };
     if (key)
-        for (auto& e : table)
-            if (strcmp(e.name, key) == 0) return e.field;
+        for (const KmSwitch& sw : g_km_switches)
+            if (strcmp(sw.key, key) == 0) return &(g_km_config.*sw.field);
     return nullptr;
 }
 int km_config_set(const char* key, int value) {

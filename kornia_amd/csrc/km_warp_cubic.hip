@@ -13,7 +13,7 @@
 // A bicubic sample reads a 4 x 4 footprint: as gathers that is four unaligned 16-byte loads per pixel and channel (64 bytes
 // requested per output pixel - the texture-address path, not HBM, bounds the generic kernel: 0.85 ms at 64x1x1080x1920 for
 // 1.06 GB of compulsory traffic), and neighbouring pixels re-request 3/4 of each other's taps.  Here the block stages the
-// source box of its KMF_T x KMF_T output tile in LDS once (16-byte row loads, zeros outside the image = what zeros padding
+// source box of its TW x TH output tile in LDS once (16-byte row loads, zeros outside the image = what zeros padding
 // reads there, so image borders need no special case) and every pixel reads its 16 taps from LDS.
 //   * arithmetic = the generic kernel's, operation for operation: positions from the lean front end (bit-identical to
 //     km_gen_coord, km_lean.h), km_cubic_coeffs, row sums t0 c0 + t1 c1 + t2 c2 + t3 c3, column sum the same way -> results are

@@ -5,7 +5,7 @@
 //
 // The gather kernel (km_warp_gm.hip) is bound by the dependent chain position -> address -> 2 x 8-byte gathers per channel -> terms of each
 // group of rows (its own ablations: two thirds of its time is that chain, not the bytes), 364 us at 256 x 3 x 512^2 where the forward - the
-// same two streams' worth of bytes - takes 281; the first LDS-staged form (km_warp_gm_lds_kernel: 32 x 32 tiles, 56 x 56 boxes through
+// same two streams' worth of bytes - takes 281; the first LDS-staged form (km_warp_gm_lds_kernel, since removed: 32 x 32 tiles, 56 x 56 boxes through
 // registers, box -> barrier -> positions -> sample) lost to it the way round 2's LDS forward lost to the gather forward.  This kernel takes
 // what made the box forward work:
 //   * a block owns a 64 x 32 region of the output, its source box (up to 80 x 40 pixels, all channels) comes by LDS-DMA - no register holds it;

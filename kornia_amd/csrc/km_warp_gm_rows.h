@@ -1,5 +1,5 @@
 // kornia_amd - the per-thread rows of the matrix gradient of the bilinear warps and its block reduction, shared by the
-// matrix-gradient kernel (km_warp_gm.hip) and its LDS-staged variant; kmg_terms also serves the one-read backward (km_warp_bwd_fused.hip).
+// matrix-gradient kernel (km_warp_gm.hip) and its box form (km_warp_gm_box.hip); kmg_terms also serves the one-read backward (km_warp_bwd_fused.hip).
 #pragma once
 
 #include "km_warp_stage.h"

@@ -17,7 +17,7 @@
 //
 // km_warp2d_pair_fwd takes the image and the first mask either in ONE launch (km_warp_pair_kernel below: the coordinate computed once per
 // pixel for both) or in TWO - the image through km_warp2d_fwd_masked, its kernels untouched, then this kernel on the same matrix and
-// switch; the image is bit-identical to km_warp2d_fwd_masked either way.  Which one runs: KM_PAIR_FUSED_DEFAULT (km_common.h).
+// switch; the image is bit-identical to km_warp2d_fwd_masked either way.  Which one runs: KM_PAIR_FUSED_DEFAULT (km_runtime.hip).
 #include "km_warp_args.h"
 #include "km_warp_host.h"
 #include "km_mask.h"

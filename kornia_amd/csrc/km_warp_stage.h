@@ -1,24 +1,17 @@
-// kornia_amd - staging of the source box of an output tile in LDS, shared by the LDS-staged forward (km_warp.hip) and
-// matrix-gradient (km_warp_gm.hip) kernels.
+// kornia_amd - staging of the source box of an output tile in LDS, shared by the box forward (km_warp.hip), the bicubic forward
+// (km_warp_cubic.hip), the fused warp + blur (km_warp_blur.hip) and the box form of the matrix gradient (km_warp_gm_box.hip).
 //
-// A 256-thread block owns a KMF_T x KMF_T tile of the OUTPUT.  kmf_tile_setup tabulates the row halves of the coordinate
+// A 256-thread block owns a TW x TH tile of the OUTPUT.  kmf_tile_setup tabulates the row halves of the coordinate
 // numerators and finds the box of source pixels the tile's footprint covers: the four tile corners pushed through the
 // forward's own coordinate arithmetic, + 1 px on every side (a projective map whose denominator keeps its sign sends the
-// tile to a convex quad, so the corners bound it up to rounding).  kmf_stage_box copies the box - all channels - into LDS
-// with 16-byte row loads, zeros outside the image (what zeros padding samples there).  Every pixel then checks that its
-// 2 x 2 footprint lies in the box (kmf_in_box) and reads its taps from LDS (kmf_tap_ptr); callers fall back to gathers
+// tile to a convex quad, so the corners bound it up to rounding).  kmf_stage_box_dyn / _dma copy the box - all channels - into
+// LDS with 16-byte row pieces, zeros outside the image (what zeros padding samples there).  Every pixel then checks that its
+// 2 x 2 footprint lies in the box (kmf_in_box) and reads its taps from LDS; callers fall back to gathers
 // from global memory when the box does not fit or a footprint is not covered, so results never depend on the estimate.
 #pragma once
 
 #include "km_lean.h"
 #include "km_regtile.h"
-
-#define KMF_T 32        // output tile (square: the source box stays small under rotation)
-#define KMF_PITCH 56    // floats per staged source row (box width + alignment slack), multiple of 4
-#define KMF_ROWS 56     // staged source rows
-#define KMF_RPT (KMF_T * KMF_T / 256)   // output rows per thread
-#define KMF_RSTEP (256 / KMF_T)          // tile rows between a thread's consecutive rows
-
 
 struct KmfBox {
     bool fast;    // division operands of every row of the tile are in the safe range (kml_row_guard)
@@ -31,8 +24,8 @@ struct KmfBox {
 
 // wave 0: row table (m1 v, m4 v, m7 v, keep_v ? v : 0) + division guard; wave 1: the source box.  Needs a barrier before kmf_read_box.
 // MARGIN: extra source pixels around the 2 x 2 footprint that the consumer reads (bicubic: 1 -> columns floor(x) - 1 .. floor(x) + 2)
-// TW x TH: the output tile; PITCH x ROWS: the capacity of the staged box (the defaults are the bilinear kernels' 32 x 32 / 56 x 56)
-template <int CM, int ALIGN, int MARGIN = 0, int TW = KMF_T, int TH = KMF_T, int PITCH = KMF_PITCH, int ROWS = KMF_ROWS>
+// TW x TH: the output tile; PITCH x ROWS: the capacity of the staged box
+template <int CM, int ALIGN, int MARGIN, int TW, int TH, int PITCH, int ROWS>
 __device__ __forceinline__ void kmf_tile_setup(const KmWarpGeom<float>& g, const float (&m)[9], int j0, int i0, float4* s_rv, int* s_info, bool keep_v) {
     const int tid_ = km_tid_pinned(), lane = tid_ & 63, wave = tid_ >> 6;  // (pinned: callers walk several tiles in a loop - km_tid_pinned)
     const int W = g.W, H = g.H;
@@ -99,43 +92,6 @@ __device__ __forceinline__ KmfBox kmf_read_box(const int* s_info) {
     b.bxlo = (float)b.xs; b.bxhi = (float)(b.xs + 4 * b.nch - 2);
     b.bylo = (float)b.ys; b.byhi = (float)(b.ys + b.nrows - 2);
     return b;
-}
-
-// copy the box into s_src[row][channel][x] (KMF_PITCH floats per channel row): 16 lanes x 4 elements per source row,
-// 16 rows per pass of the block; all loads of a thread are issued before the first LDS store.  Needs a barrier after.
-// oob[c]: the value staged outside the image (0 for zeros padding; the fill value where the consumer subtracts it from every tap)
-template <typename T, int NC>
-__device__ __forceinline__ void kmf_stage_box(const T* __restrict__ src_b, size_t src_plane, int W, int H, const KmfBox& bx, float* s_src,
-                                              const float (&oob)[NC]) {
-    static_assert(KMF_T == 32 && (KMF_PITCH % 4) == 0 && KMF_PITCH / 4 <= 16, "16 lanes x 16 bytes cover a staged row");
-    const int tid = threadIdx.x, ck = tid & 15, r0 = tid >> 4;
-    const int x = bx.xs + 4 * ck;
-    const bool col_in = (ck < bx.nch) && (x >= 0) && (x + 3 < W);  // W % 4 == 0 and xs % 4 == 0: a chunk is inside or outside as a whole
-    constexpr int NPASS = (KMF_ROWS + 15) / 16;
-    float v[NPASS][NC][4];
-#pragma unroll
-    for (int ps = 0; ps < NPASS; ++ps) {
-        const int r = r0 + 16 * ps, y = bx.ys + r;
-        const bool inb = col_in && (r < bx.nrows) && (y >= 0) && (y < H);
-        const uint32_t off = inb ? (uint32_t)y * (uint32_t)W + (uint32_t)x : 0u;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            if (inb) km_ld4(km_at(src_b + c * src_plane, off), v[ps][c]);
-            else { v[ps][c][0] = oob[c]; v[ps][c][1] = oob[c]; v[ps][c][2] = oob[c]; v[ps][c][3] = oob[c]; }
-        }
-    }
-#pragma unroll
-    for (int ps = 0; ps < NPASS; ++ps) {
-        const int r = r0 + 16 * ps;
-        if ((ck < bx.nch) && (r < bx.nrows)) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                float* q = s_src + (r * NC + c) * KMF_PITCH + 4 * ck;
-                KM_CHECK_ALIGNED(q, 16);
-                *reinterpret_cast<float4*>(q) = make_float4(v[ps][c][0], v[ps][c][1], v[ps][c][2], v[ps][c][3]);
-            }
-        }
-    }
 }
 
 // The same copy for any box capacity (PITCH floats per staged row): 16 or 32 lanes per source row, chosen per block from the
@@ -208,10 +164,4 @@ __device__ __forceinline__ bool kmf_in_box(const KmlTaps& t, const KmfBox& bx) {
 // the 4 x 4 footprint of a bicubic sample at floor (xf, yf) lies in the staged box
 __device__ __forceinline__ bool kmf_in_box_cubic(float xf, float yf, const KmfBox& bx) {
     return (xf >= bx.bxlo + 1.0f) & (xf <= bx.bxhi - 1.0f) & (yf >= bx.bylo + 1.0f) & (yf <= bx.byhi - 1.0f);
-}
-// LDS address of the north-west tap of channel 0 (channel c: + c * KMF_PITCH ; next row: + NC * KMF_PITCH); !valid: the box origin
-template <int NC>
-__device__ __forceinline__ const float* kmf_tap_ptr(const float* s_src, const KmlTaps& t, const KmfBox& bx, bool valid) {
-    const int xi = valid ? KM_F2I(t.xf) - bx.xs : 0, yi = valid ? KM_F2I(t.yf) - bx.ys : 0;
-    return s_src + __mul24(yi, NC * KMF_PITCH) + xi;
 }

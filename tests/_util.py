@@ -1,6 +1,8 @@
 """Shared test helpers: seeded inputs in the shape of BASELINE.json's configs."""
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 
@@ -55,3 +57,19 @@ def golden(name: str):
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name + ".npz")
     with np.load(path) as z:
         return {k: z[k] for k in z.files}
+
+
+@contextlib.contextmanager
+def launch_policy(**cfg):
+    """``with launch_policy(warp_bwd_fused=0, warp_gm_algo=3): ...``: km_config_set(key, value) for each item (the keys of
+    include/kornia_amd.h), the previous values put back in reverse order on the way out, whatever the body raised."""
+    from kornia_amd import _native as N
+
+    lib, prev = N.lib(), []
+    try:
+        for k, v in cfg.items():
+            prev.append((k, lib.km_config_set(k.encode(), int(v))))
+        yield
+    finally:
+        for k, v in reversed(prev):
+            lib.km_config_set(k.encode(), v)

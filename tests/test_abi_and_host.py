@@ -389,6 +389,88 @@ def test_filter_entry_points_host_contract_without_a_gpu():
     rejected(hyst(B=2, H=1 << 21, W=1 << 21), b"km_canny_hysteresis_sweep: grid too large")  # 64 x 64 tiles
 
 
+# ---- launch policy: the keys of km_config_set / km_config_get, their environment variables and defaults (csrc/km_runtime.hip, g_km_switches) ----
+POLICY = {  # key: (environment variable, value when the variable is not set)
+    "traversal_fixed": ("KM_TRAVERSAL", 0), "warp_fwd_algo": ("KM_WARP_FWD_ALGO", 0), "warp_gm_algo": ("KM_WARP_GM_ALGO", 0),
+    "warp_bwd_generic": ("KM_WARP_BWD_ALGO", 0), "warp_bwd_fused": ("KM_WARP_BWD_FUSED", 1), "sep_lds": ("KM_SEP_ALGO", 0),
+    "sg_generic": ("KM_SG_ALGO", 0), "blur_rows": ("KM_BLUR_ROWS", 0), "warp_bwd_no_scan": ("KM_WARP_BWD_SCAN", 0), "pair_fused": ("KM_PAIR_ALGO", 2),
+}
+POLICY_DEFAULTS = {key: default for key, (_, default) in POLICY.items()}
+
+_POLICY_CHILD = """
+import ctypes, json, sys
+lib = ctypes.CDLL(sys.argv[1])
+lib.km_config_get.argtypes, lib.km_config_set.argtypes = [ctypes.c_char_p], [ctypes.c_char_p, ctypes.c_int]
+keys = sys.argv[2:]
+first = {k: lib.km_config_get(k.encode()) for k in keys}
+prev = {k: lib.km_config_set(k.encode(), 40 + i) for i, k in enumerate(keys)}
+then = {k: lib.km_config_get(k.encode()) for k in keys}
+print(json.dumps([first, prev, then]))
+"""
+
+
+def _policy_in_a_fresh_process(env):
+    """(values read first, values km_config_set(key, 40 + i) returned, values read after it) in a child process that has of the KM_*
+    variables exactly `env`; the child loads the library with ctypes alone and never opens a device"""
+    import json
+    import subprocess
+    import sys
+
+    from kornia_amd import _native
+
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("KM_")}
+    res = subprocess.run([sys.executable, "-c", _POLICY_CHILD, _native.library_path(), *POLICY], env={**clean, **env}, capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0, res.stderr[-2000:]
+    return json.loads(res.stdout)
+
+
+def test_launch_policy_defaults_set_and_get():
+    first, prev, then = _policy_in_a_fresh_process({})
+    assert first == POLICY_DEFAULTS
+    assert prev == POLICY_DEFAULTS  # km_config_set returns the previous value ...
+    assert then == {k: 40 + i for i, k in enumerate(POLICY)}  # ... and km_config_get then returns the new one
+
+
+@pytest.mark.parametrize("spellings", [
+    dict(traversal_fixed=("fixed", 1), warp_fwd_algo=("rows", 4), warp_gm_algo=("generic", 1), warp_bwd_generic=("generic", 1), warp_bwd_fused=("0", 0),
+         sep_lds=("lds", 1), sg_generic=("generic", 1), blur_rows=("16", 16), warp_bwd_no_scan=("0", 1), pair_fused=("two", 0)),
+    dict(warp_fwd_algo=("box", 3), warp_gm_algo=("rows", 3), pair_fused=("fused", 1), blur_rows=("32", 32), warp_bwd_fused=("1", 1), warp_bwd_no_scan=("1", 0)),
+    dict(warp_fwd_algo=("generic", 1), traversal_fixed=("alternate", 0), pair_fused=("auto", 2), blur_rows=("rows", 0), sep_lds=("reg", 0)),
+], ids=["every-switch", "second-spellings", "unlisted-spellings"])
+def test_launch_policy_is_decoded_from_the_environment(spellings):
+    """The variables are read once, by the first character of their value (KM_BLUR_ROWS: atoi)."""
+    first, _, _ = _policy_in_a_fresh_process({POLICY[key][0]: text for key, (text, _) in spellings.items()})
+    assert first == {**POLICY_DEFAULTS, **{key: value for key, (_, value) in spellings.items()}}
+
+
+def test_removed_spellings_read_as_unset():
+    """The LDS-staged matrix gradient and the separable pyrdown are gone: their spellings select nothing."""
+    first, _, _ = _policy_in_a_fresh_process({"KM_WARP_GM_ALGO": "lds", "KM_PYRDOWN_ALGO": "separable"})
+    assert first == POLICY_DEFAULTS
+
+
+def test_unknown_policy_keys_are_refused():
+    from kornia_amd import _native
+
+    lib = _native.lib()
+    for key in (b"pyrdown_separable", b"warp_gm", b"", None):
+        for call in (lambda: lib.km_config_get(key), lambda: lib.km_config_set(key, 1)):
+            assert call() == -1 and b"unknown key" in lib.km_last_error(), key
+
+
+def test_launch_policy_keys_are_listed_once():
+    """The table of km_runtime.hip, the struct the launchers read and the keys named in include/kornia_amd.h are the same set."""
+    csrc = os.path.join(ROOT, "kornia_amd", "csrc")
+    rows = re.findall(r'^\s*\{"(\w+)", &KmConfig::(\w+), "(KM_\w+)", [\w<>\']+\},', open(os.path.join(csrc, "km_runtime.hip")).read(), flags=re.M)
+    assert {key: env for key, _, env in rows} == {key: env for key, (env, _) in POLICY.items()} and len(rows) == len(POLICY)
+    assert all(key == field for key, field, _ in rows)
+    struct = re.search(r"struct KmConfig \{(.*?)\};", open(os.path.join(csrc, "km_common.h")).read(), flags=re.S).group(1)
+    assert sorted(re.findall(r"^\s*int (\w+);", struct, flags=re.M)) == sorted(POLICY)
+    header = open(os.path.join(ROOT, "include", "kornia_amd.h")).read()
+    comment = header[header.index("/* Launch policy."):header.index("int km_config_set(")]
+    assert sorted(re.findall(r'"(\w+)"', comment)) == sorted(POLICY)
+
+
 def test_launch_contract():
     """_native.launch(name, device, *args): the entry point gets (*args, stream_ptr(device)) under exactly one device_guard(device); 0 returns
     None without asking for the error text, anything else raises NativeLibraryError with the name, the code and km_last_error().  `lib`,

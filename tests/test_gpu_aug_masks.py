@@ -10,7 +10,7 @@ tests/make_golden_aug_masks.py) and bit for bit against the compositions they re
 import pytest
 import torch
 
-from _util import golden
+from _util import golden, launch_policy
 
 pytestmark = pytest.mark.gpu
 
@@ -225,29 +225,23 @@ def test_errors():
 def test_one_launch_and_two_launch_pair_are_the_same(img_dtype):
     """km_warp2d_pair_fwd as one launch (km_warp_pair_kernel) and as two (the image's own forward + the mask kernel): the same bits, for every
     padding, both interpolations, both coordinate generators, with and without the switch, one and three mask channels."""
-    from kornia_amd import _native as N
     import kornia_amd.augmentation as A
 
     B, H, W = 3, 19, 33
     g = torch.Generator().manual_seed(21)
     x = torch.rand(B, 3, H, W, generator=g).to(img_dtype).cuda()
     lab = torch.randint(0, 300, (B, 3, H, W), generator=g)
-    lib = N.lib()
-    prev = lib.km_config_set(b"pair_fused", 1)
-    try:
-        for mod in _affine_and_persp(B, H, W, 17) + [A.RandomAffine(20.0, resample="nearest", padding_mode="reflection", p=0.5)]:
-            params = mod.forward_parameters((B, 3, H, W))
-            p = mod._device_params(params, x.device, False)
-            m, _, apply = mod._chain(p, x.device, H, W)
-            for mk in (lab[:, :1].to(torch.uint8).cuda(), lab.cuda(), (lab[:, :2] > 150).cuda()):
-                kw = dict(affine=mod._AFFINE, resample=mod.resample, padding_mode=mod.padding_mode, fill_value=0.7, apply=apply)
-                res = []
-                for fused in (1, 0):
-                    lib.km_config_set(b"pair_fused", fused)
+    for mod in _affine_and_persp(B, H, W, 17) + [A.RandomAffine(20.0, resample="nearest", padding_mode="reflection", p=0.5)]:
+        params = mod.forward_parameters((B, 3, H, W))
+        p = mod._device_params(params, x.device, False)
+        m, _, apply = mod._chain(p, x.device, H, W)
+        for mk in (lab[:, :1].to(torch.uint8).cuda(), lab.cuda(), (lab[:, :2] > 150).cuda()):
+            kw = dict(affine=mod._AFFINE, resample=mod.resample, padding_mode=mod.padding_mode, fill_value=0.7, apply=apply)
+            res = []
+            for fused in (1, 0):
+                with launch_policy(pair_fused=fused):
                     res.append(A.warp_pair(x, mk, m, **kw))
-                assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1]), (type(mod).__name__, mod.padding_mode, mk.dtype)
-    finally:
-        lib.km_config_set(b"pair_fused", prev)
+            assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1]), (type(mod).__name__, mod.padding_mode, mk.dtype)
 
 
 def test_many_mask_planes():

@@ -3,6 +3,8 @@ sobel, transform_points) against the CPU oracle, through the kornia-compatible A
 import pytest
 import torch
 
+from _util import launch_policy
+
 pytestmark = pytest.mark.gpu
 
 BORDERS = ["constant", "reflect", "replicate", "circular"]
@@ -494,17 +496,12 @@ def test_half_precision_blur_strip_heights(dtype, K, border, shape, monkeypatch)
     x = torch.rand(*shape, generator=g).to(dtype).cuda()
     kx, ky = torch.rand(1, K, generator=g).cuda(), torch.rand(1, K, generator=g).cuda()
     go = torch.rand(*shape, generator=g).to(dtype).cuda()
-    from kornia_amd import _native as N
-
     res = {}
     for rows in ("8", "16", "32"):
-        prev = N.lib().km_config_set(b"blur_rows", int(rows))  # (the KM_BLUR_ROWS switch: read once at load, set explicitly here)
-        try:
+        with launch_policy(blur_rows=int(rows)):  # (the KM_BLUR_ROWS switch: read once at load, set explicitly here)
             xg = x.clone().requires_grad_()
             out = K_.filter2d_separable(xg, kx, ky, border)
             out.backward(go)
-        finally:
-            N.lib().km_config_set(b"blur_rows", prev)
         res[rows] = (out.detach(), xg.grad)
     assert torch.equal(res["8"][0], res["32"][0]) and torch.equal(res["8"][1], res["32"][1])
     assert torch.equal(res["16"][0], res["32"][0]) and torch.equal(res["16"][1], res["32"][1])

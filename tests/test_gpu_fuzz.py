@@ -7,6 +7,8 @@ import math
 import pytest
 import torch
 
+from _util import launch_policy
+
 pytestmark = pytest.mark.gpu
 
 
@@ -108,9 +110,7 @@ def test_random_box_forward_against_the_gather_kernel(seed):
     import random
 
     import kornia_amd as K
-    from kornia_amd import _native as N
 
-    lib = N.lib()
     rnd = random.Random(100 + seed)
     g = torch.Generator().manual_seed(100 + seed)
     for _ in range(10):
@@ -141,16 +141,13 @@ def test_random_box_forward_against_the_gather_kernel(seed):
             fn, M = "affine", M[:1]  # (only warp_affine takes a shared matrix, like the reference)
         outs = []
         for algo in (3, 4):
-            prev = lib.km_config_set(b"warp_fwd_algo", algo)
-            try:
+            with launch_policy(warp_fwd_algo=algo):
                 if fn == "persp":
                     o = K.warp_perspective(x.cuda(), M.cuda(), (h, w), "bilinear", "zeros", align)
                 elif fn == "affine":
                     o = K.warp_affine(x.cuda(), M[:, :2].contiguous().cuda(), (h, w), "bilinear", "zeros", align)
                 else:
                     o = K.homography_warp(x.cuda(), M.cuda(), (h, w), "bilinear", "zeros", align)
-            finally:
-                lib.km_config_set(b"warp_fwd_algo", prev)
             outs.append(torch.nan_to_num(o.float(), nan=12345.0, posinf=23456.0, neginf=-23456.0))
         assert torch.equal(outs[0], outs[1]), (kind, fn, (B, C, H, W), (h, w), dtype, align, (outs[0] - outs[1]).abs().max().item())
 

@@ -16,7 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _util import flagship_homographies
+from _util import flagship_homographies, launch_policy
 
 pytestmark = pytest.mark.gpu
 
@@ -28,19 +28,6 @@ def _lib():
     from kornia_amd import _native as N
 
     return N.lib()
-
-
-def _with_config(cfg, fn):
-    """fn() under km_config_set(key, value) for each item of cfg; the previous values are restored in a finally (test_gpu_warp_fused._run)"""
-    lib = _lib()
-    prev = []
-    try:
-        for k, v in cfg.items():
-            prev.append((k, lib.km_config_set(k.encode(), v)))
-        return fn()
-    finally:
-        for k, v in reversed(prev):
-            lib.km_config_set(k.encode(), v)
 
 
 def _ulp(ref, dt):
@@ -86,7 +73,7 @@ POLICIES = {
     "generic": {"warp_bwd_generic": 1},                   # the fp32-atomic scatter
     "gm_box": {"warp_bwd_fused": 0, "warp_gm_algo": 0},   # matrix gradient: box form (fp32 only) or rows / gather in 16-bit
     "gm_generic": {"warp_bwd_fused": 0, "warp_gm_algo": 1},
-    "gm_rows": {"warp_bwd_fused": 0, "warp_gm_algo": 2},
+    "gm_rows": {"warp_bwd_fused": 0, "warp_gm_algo": 3},
 }
 
 
@@ -116,7 +103,8 @@ def _grads(op, x, M, go, cfg, need=("x", "M")):
         op(xg, Mg).backward(go.cuda())
         return (None if xg.grad is None else xg.grad.cpu()), (None if Mg.grad is None else Mg.grad.cpu())
 
-    return _with_config(cfg, run)
+    with launch_policy(**cfg):
+        return run()
 
 
 def _matrices(fn, B, H, W, h, w, g, shared=False):
@@ -493,7 +481,8 @@ def _sep_grad(x16, kx, ky, border, go16, cfg=None):
         K_.filters.filter2d_separable(xg, kx.cuda(), ky.cuda(), border).backward(go16.cuda())
         return xg.grad.cpu()
 
-    return _with_config(cfg or {}, run)
+    with launch_policy(**(cfg or {})):
+        return run()
 
 
 @pytest.mark.parametrize("Bk", [1, "B"])
@@ -587,7 +576,8 @@ def test_spatial_gradient_adjoint(oracle, dt, order, generic):
             K_.spatial_gradient(xg, "sobel", order).backward(go16.cuda())
             return xg.grad.cpu()
 
-        got = _with_config({"sg_generic": generic}, run)
+        with launch_policy(sg_generic=generic):
+            got = run()
         ref = sum(_adjoint(go16[:, :, j], kern[j:j + 1], "replicate") for j in range(kern.shape[0])).to(dt)
         _assert_composition(got, ref, dt, f"order {order} W={W} generic={generic}", exact_bf16=False)
 

@@ -6,7 +6,7 @@ import math
 import pytest
 import torch
 
-from _util import flagship_homographies, rotation_affines
+from _util import flagship_homographies, launch_policy, rotation_affines
 
 pytestmark = pytest.mark.gpu
 
@@ -400,9 +400,7 @@ def test_box_forward_is_bit_identical(oracle, C, dtype):
     not fit -> the gather path inside the kernel), minification, magnification, a map that leaves the image, output sizes that are not
     multiples of the tile, both align_corners, affine / homography coordinate modes, the per-sample switch."""
     import kornia_amd as K
-    from kornia_amd import _native as N
 
-    lib = N.lib()
     g = torch.Generator().manual_seed(43)
     B, H, W = 7, 72, 96
     x = torch.rand(B, C, H, W, generator=g).to(dtype)
@@ -422,11 +420,8 @@ def test_box_forward_is_bit_identical(oracle, C, dtype):
     def both(fn):
         outs = []
         for algo in (3, 4):
-            prev = lib.km_config_set(b"warp_fwd_algo", algo)
-            try:
+            with launch_policy(warp_fwd_algo=algo):
                 outs.append(fn())
-            finally:
-                lib.km_config_set(b"warp_fwd_algo", prev)
         assert torch.equal(outs[0], outs[1])
         return outs[0]
 
@@ -449,29 +444,21 @@ def test_16_bit_storage_is_the_fp32_result_rounded_once(dtype):
     gather rows, generic sampler, the blur).  On the device the compiler used to fuse the last fma of the accumulation with the conversion
     (v_fma_mixlo_f16: the exact sum rounded to f16 once) in some kernels and not in others: 1 ulp apart at ties, ~1e-5 of the pixels."""
     import kornia_amd as K
-    from kornia_amd import _native as N
 
-    lib = N.lib()
     g = torch.Generator().manual_seed(105)
     x = torch.rand(3, 3, 72, 100, generator=g).to(dtype)
     A = torch.tensor([[[0.9480, -0.0047, 2.6100], [-0.0321, 0.9642, 1.1322]]]).repeat(3, 1, 1)
     A[1, :, :2] = torch.tensor([[0.81, 0.55], [-0.55, 0.81]])   # a rotation: the square tiles
     A[2] *= 0.6                                                   # minification: gather rows inside the box kernel
     for algo in (3, 4, 1):
-        prev = lib.km_config_set(b"warp_fwd_algo", algo)
-        try:
+        with launch_policy(warp_fwd_algo=algo):
             got = K.warp_affine(x.cuda(), A.cuda(), (96, 136), "bilinear", "zeros", False)
             ref = K.warp_affine(x.float().cuda(), A.cuda(), (96, 136), "bilinear", "zeros", False).to(dtype)
-        finally:
-            lib.km_config_set(b"warp_fwd_algo", prev)
         assert torch.equal(got, ref), (algo, (got.float() - ref.float()).abs().max().item(), int((got != ref).sum()))
     got = K.gaussian_blur2d(x.cuda(), (5, 5), (1.5, 1.5))
     # (the reference materialises the row pass in the storage type: the fp32 run of the same values is not the comparison for the blur;
     # what is pinned here is that the result does not depend on the fusion - the strip height changes the code the compiler sees)
     for rows in (8, 16, 32):
-        prev = lib.km_config_set(b"blur_rows", rows)
-        try:
+        with launch_policy(blur_rows=rows):
             again = K.gaussian_blur2d(x.cuda(), (5, 5), (1.5, 1.5))
-        finally:
-            lib.km_config_set(b"blur_rows", prev)
         assert torch.equal(got, again), rows

@@ -23,7 +23,7 @@ import math
 import pytest
 import torch
 
-from _util import flagship_homographies
+from _util import flagship_homographies, launch_policy
 
 pytestmark = pytest.mark.gpu
 
@@ -93,13 +93,9 @@ def _grads(name, fused, x=None, M=None, go=None):
     """(grad_x, grad_M) through the public API, the one-read backward on (the workspace form) or off (the two launches)"""
     x0, M0, go0 = _inputs(name)
     x, M, go = (x0 if x is None else x), (M0 if M is None else M), (go0 if go is None else go)
-    lib = _lib()
-    prev = lib.km_config_set(b"warp_bwd_fused", 1 if fused else 0)
-    try:
+    with launch_policy(warp_bwd_fused=1 if fused else 0):
         xg, Mg = x.cuda().requires_grad_(), M.cuda().requires_grad_()
         _op(name)(xg, Mg).backward(go.cuda())
-    finally:
-        lib.km_config_set(b"warp_bwd_fused", prev)
     return xg.grad.cpu(), Mg.grad.cpu()
 
 

@@ -4,7 +4,7 @@ kernels (tests/test_emulated_kernels.py)."""
 import pytest
 import torch
 
-from _util import flagship_homographies, rotation_affines, smooth_image
+from _util import flagship_homographies, launch_policy, rotation_affines, smooth_image
 
 pytestmark = pytest.mark.gpu
 
@@ -17,13 +17,9 @@ def _lib():
 
 def _run(fn, x, M, go, fused, **kw):
     """(grad_x, grad_M) of fn(x, M, ...) through the public API with the one-read backward on / off"""
-    lib = _lib()
-    prev = lib.km_config_set(b"warp_bwd_fused", 1 if fused else 0)
-    try:
+    with launch_policy(warp_bwd_fused=1 if fused else 0):
         xg, Mg = x.cuda().requires_grad_(), M.cuda().requires_grad_()
         fn(xg, Mg, **kw).backward(go.cuda())
-    finally:
-        lib.km_config_set(b"warp_bwd_fused", prev)
     return xg.grad.cpu(), Mg.grad.cpu()
 
 
@@ -338,18 +334,14 @@ def test_launch_policy_without_the_scan_has_the_accelerator_kernels_semantics():
     the CPU reference's (the fixture above)."""
     import kornia_amd as K
     from _util import golden
-    from kornia_amd import _native as N
 
     d = {k: torch.from_numpy(v) for k, v in golden("nonfinite_outside").items()}
     go = d["persp__go"].clone()
     bad = ~torch.isfinite(go)
     assert bad.any()
     fn = lambda a, m: K.warp_perspective(a, m, (96, 160))
-    prev = N.lib().km_config_set(b"warp_bwd_no_scan", 1)
-    try:
+    with launch_policy(warp_bwd_no_scan=1):
         gx, gM = _run(fn, d["persp__x"], d["persp__M"], go, True)
-    finally:
-        N.lib().km_config_set(b"warp_bwd_no_scan", prev)
     gx0, gM0 = _run(fn, d["persp__x"], d["persp__M"], torch.where(bad, torch.zeros_like(go), go), True)
     assert torch.isfinite(gM).all() and torch.isfinite(gx).all()
     assert _rel(gM, gM0) <= 1e-6 and torch.equal(gx, gx0)

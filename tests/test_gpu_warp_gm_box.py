@@ -9,7 +9,7 @@ import math
 import pytest
 import torch
 
-from _util import flagship_homographies, rotation_affines
+from _util import flagship_homographies, launch_policy, rotation_affines
 
 pytestmark = pytest.mark.gpu
 
@@ -20,10 +20,8 @@ def _rel(a, b):
 
 def _grad_wrt_matrix(kind, x, M, go, ds, align, algo=0):
     import kornia_amd as K
-    from kornia_amd import _native as N
 
-    prev = N.lib().km_config_set(b"warp_gm_algo", algo)
-    try:
+    with launch_policy(warp_gm_algo=algo):
         Mg = M.cuda().requires_grad_()
         xc = x.cuda()  # (no gradient wrt the image: the matrix-gradient-only launch)
         if kind == "perspective":
@@ -34,8 +32,6 @@ def _grad_wrt_matrix(kind, x, M, go, ds, align, algo=0):
             out = K.homography_warp(xc, Mg, ds, "bilinear", "zeros", align)
         out.backward(go.cuda())
         return Mg.grad.cpu()
-    finally:
-        N.lib().km_config_set(b"warp_gm_algo", prev)
 
 
 def _oracle_grad(oracle, kind, x, M, go, ds, align):

@@ -109,7 +109,8 @@ def _raw(guard_site, shape, dtype, zero=False):
 
 # ---- warps ----------------------------------------------------------------------------------------------------------------------------
 from test_gpu_half_grads import (FLOAT_TILE_MULT, POLICIES, _check_warp, _matrices, _oracle_bwd, _output_pixels_per_source_pixel, _rel, _ulp,  # noqa: E402
-                                 _warp_op, _with_config, _within_ulps)
+                                 _warp_op, _within_ulps)
+from _util import launch_policy  # noqa: E402
 
 WARP_SHAPES = [(70, 93, 37, 53), (70, 93, 66, 68), (64, 128, 64, 64)]  # H, W, h, w: ragged owner tiles and box regions, W % 4 != 0; the 16-byte paths
 WARP_PADS = ["zeros", "border", "reflection", "fill"]
@@ -165,7 +166,8 @@ def _warp_case(oracle, fn, dt, C, shape, pad, policy, need, mode="bilinear", sha
                 if "M" in need:
                     res["acc_gM"] = Mg.grad.cpu()
 
-    _with_config(cfg, run)
+    with launch_policy(**cfg):
+        run()
     gx_name = "gx" if "gx" in res else "atm_gx"
     Mo = M.expand(B, -1, -1).contiguous() if shared else M
     if dt == F32:
@@ -189,7 +191,8 @@ def _warp_case(oracle, fn, dt, C, shape, pad, policy, need, mode="bilinear", sha
     else:
         # the 16-bit forward is the fp32 path's result rounded once (test_gpu_warp.py::test_16_bit_storage_is_the_fp32_result_rounded_once);
         # the gradients: the whole contract of test_gpu_half_grads.py, against the fp32 path and the oracle
-        y32 = _with_config(cfg, lambda: op(xd.float(), Md).to(dt).cpu())
+        with launch_policy(**cfg):
+            y32 = op(xd.float(), Md).to(dt).cpu()
         assert same_bits(res["y"], y32), "the 16-bit forward is not the fp32 path's rounded once"
         if need:
             gx, gM = _check_warp(oracle, fn, dt, x, M, go, (h, w), cfg, need=need, mode=mode, pad=pad, align=align, fill=fill, tag="table")
@@ -247,7 +250,8 @@ def _case_warp2d_bwd_abi(oracle):
         N.check(_lib().km_warp2d_bwd(go.data_ptr(), x.data_ptr(), m.data_ptr(), gsrc.data_ptr(), gm.data_ptr(), B, C, H, W, h, w, B, 2, 1, 1, 0, 1, None, 0,
                                      _stream()), "km_warp2d_bwd")
     xg, mg = x.detach().requires_grad_(), m.view(B, 3, 3).detach().requires_grad_()
-    _with_config(POLICIES["tiled"], lambda: K.homography_warp(xg, mg, (h, w), "bilinear", "zeros", True).backward(go))
+    with launch_policy(**POLICIES["tiled"]):
+        K.homography_warp(xg, mg, (h, w), "bilinear", "zeros", True).backward(go)
     assert torch.allclose(gsrc.cpu(), xg.grad.cpu(), atol=2e-5, rtol=1e-5)
     assert _rel(gm.view(B, 3, 3).cpu(), mg.grad.cpu()) <= 5e-5
     return {"gsrc": gsrc.cpu(), "acc_gm": gm.cpu()}

@@ -16,8 +16,8 @@ import pytest
 import torch
 
 import nonfinite_pixel_cases as P
-from _util import golden
-from test_gpu_half_grads import _with_config, _within_ulps
+from _util import golden, launch_policy
+from test_gpu_half_grads import _within_ulps
 from test_gpu_median import unaligned
 
 pytestmark = pytest.mark.gpu
@@ -77,8 +77,6 @@ def _policies(name):
         return [{"sep_lds": 1}, {"blur_rows": 8}, {"blur_rows": 16}, {"blur_rows": 32}]
     if name.startswith(("sg_", "sobel")):
         return [{"sg_generic": 1}]
-    if name.startswith("pyr"):
-        return [{"pyrdown_separable": 1}, {"pyrdown_separable": 1, "blur_rows": 16}]
     if name.startswith(("warp_", "homography_warp", "remap", "grid_sample")):
         return [{"warp_fwd_algo": 1}, {"warp_fwd_algo": 3}, {"warp_fwd_algo": 4}]
     return []
@@ -118,7 +116,8 @@ def test_forward_matches_the_reference_on_every_path(name):
                     agree(other[0], ref[i], tol, what + ("one element past an aligned address",), v32)
                     assert same_bits(other, out, tol), (what, "one element past an aligned address")
                 for cfg in _policies(name):
-                    got = _with_config(cfg, lambda: run(K, x.cuda()))
+                    with launch_policy(**cfg):
+                        got = run(K, x.cuda())
                     agree(got[0], ref[i], tol, what + (str(cfg),), v32)
                     assert same_bits(got, out, tol), (what, cfg)
 
@@ -161,7 +160,8 @@ def test_planted_grad_out_through_the_linear_adjoints(name):
             assert same_bits(gx[1:], alone) and torch.isfinite(alone).all(), (name, sn, kind, "the clean sample")
             assert same_bits(grad(unaligned(P.image(sn, None))), gx, tol), (name, sn, kind, "unaligned")
             for cfg in _policies(name):
-                got = _with_config(cfg, lambda: grad(P.image(sn, None).cuda()))
+                with launch_policy(**cfg):
+                    got = grad(P.image(sn, None).cuda())
                 agree(got[0], ref[i], tol, (name, sn, kind, str(cfg)))
                 assert same_bits(got, gx, tol), (name, sn, kind, cfg)
 
@@ -274,7 +274,8 @@ def test_warp_gradients_with_a_non_finite_pixel(pad, sn):
         check(ox, oM, rx, rM, (pad, sn, kind, "unaligned"))
         assert same_bits(ox, gx, 1e-6), (pad, sn, kind, "unaligned")
         for cfg in _BWD_POLICIES:
-            px, pM = _with_config(cfg, lambda: grads(P.image(sn, kind).cuda()))
+            with launch_policy(**cfg):
+                px, pM = grads(P.image(sn, kind).cuda())
             check(px, pM, rx, rM, (pad, sn, kind, str(cfg)))
             # (two kernels sum an entry's up to nine products of |grad_out| <= 2 in different orders: 1e-5, the image gradient's bound above)
             assert same_bits(px, gx, 1e-5), (pad, sn, kind, cfg)
