@@ -253,7 +253,9 @@ int km_color_jitter_fwd(const void* x, void* y, const void* params, double* gray
  * Replaces F.pad + F.conv2d(groups = Bk*C) of filter2d (kornia/filters/filter.py:131-150).
  *   x (B,C,H,W) dtype; k (Bk,kH,kW) prepared taps (flipped for 'conv', normalised, rounded to the
  *   input dtype) stored in the compute dtype; sample b uses kernel b % Bk (filter.py:141-142);
- *   same = 1: output (B,C,H,W) with `border`; same = 0 ('valid'): (B,C,H-kH+1,W-kW+1). */
+ *   same = 1: output (B,C,H,W) with `border`; same = 0 ('valid'): (B,C,H-kH+1,W-kW+1).
+ *   Which kernels run (register-tiled 3/5/7, LDS-tiled up to 31 x 31, generic beyond) never changes a result - forward and input gradient
+ *   bit for bit, the tap gradient up to the order of its fp64 sums -, and the policy key "sep_lds" = 1 also selects the generic dense kernels. */
 int km_filter2d_fwd(const void* x, const void* k, void* y, int B, int C, int H, int W, int Bk, int kH, int kW, int border,
                     int same, int dtype, void* stream);
 int km_filter2d_bwd_input(const void* gy, const void* k, void* gx, int B, int C, int H, int W, int Bk, int kH, int kW,

@@ -17,6 +17,8 @@
 //   km_filter2d_fwd_kernel        generic kH x kW (any size / border / Bk), direct loads.
 //   km_filter2d_bwd_input_kernel  generic adjoint, gather form (no atomics, deterministic).
 //   km_filter2d_bwd_kernel_kernel gradient wrt the taps (fp64 accumulation).
+// The three generic kernels serve what neither km_filter2d_fast.hip (square odd 3 / 5 / 7) nor km_filter2d_tiled.hip (up to 31 x 31)
+// takes, and everything under km_config().sep_lds.
 #include <stdlib.h>
 
 #include "km_filter_host.h"
@@ -439,8 +441,6 @@ static size_t km_sep_bwd_lds(int kH, int kW, int same) {
     return (VH * UW + EH * UW + KM_FS_TH * UW + KM_FS_TH * EW + kW + kH) * sizeof(R);
 }
 
-#define KM_LDS_LIMIT (64 * 1024)
-
 template <typename T>
 static int km_sep_run(const KmFilterCall& g, bool bwd, const void* x, const void* kx, const void* ky, void* y) {
     typedef typename KmTraits<T>::R R;
@@ -507,6 +507,7 @@ int km_filter2d_fwd(const void* x, const void* k, void* y, int B, int C, int H, 
     if (km_filter_validate("km_filter2d_fwd", c)) return -1;
     KM_REQUIRE(x && k && y, "km_filter2d_fwd: null pointer");
     if (!km_config().sep_lds && km_filter2d_fast_supported(c, x, y)) return km_filter2d_fast_run(c, x, k, y, border, 0);
+    if (!km_config().sep_lds && km_filter2d_tiled_supported(c)) return km_filter2d_tiled_run(c, x, k, y, 0);  // up to 31 x 31: LDS tiles
     return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(c, 0, x, nullptr, k, y, nullptr); });
 }
 
@@ -521,10 +522,19 @@ int km_filter2d_bwd_input(const void* gy, const void* k, void* gx, int B, int C,
     // square odd 3/5/7 kernels: interior by the register-tiled kernel on the zero-extended gradient with the rotated taps
     // (for constant padding that is the whole adjoint), then the pad-wide frame by the exact pre-image kernel
     // frame width: reflect folds padded coordinate -p onto pixel p for p = 1..pad, so pixels 0..pad are affected
-    const int pd = (kH - 1) / 2 + 1;
+    // (the larger of the front and rear pad of both axes, + 1: an even or rectangular kernel pads more behind than in front)
+    const int rb = kH - 1 - (kH - 1) / 2, rr = kW - 1 - (kW - 1) / 2;
+    const int pd = (rb > rr ? rb : rr) + 1;
     if (!km_config().sep_lds && km_filter2d_fast_supported(c, gy, gx) && H > 2 * pd && W > 2 * pd) {
         const int rc = km_filter2d_fast_run(c, gy, k, gx, KM_BORDER_CONSTANT, 1);
         if (rc != 0 || border == KM_BORDER_CONSTANT) return rc;
+        return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_frame_run<KM_TAG_T(t)>(c, gy, k, gx, pd); });
+    }
+    // the other kernels up to 31 x 31: the same split with the LDS-tiled kernel; 'valid' has no fold and no frame
+    const bool folds = same && border != KM_BORDER_CONSTANT;
+    if (!km_config().sep_lds && km_filter2d_tiled_supported(c) && (!folds || (H > 2 * pd && W > 2 * pd))) {
+        const int rc = km_filter2d_tiled_run(c, gy, k, gx, 1);
+        if (rc != 0 || !folds) return rc;
         return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_frame_run<KM_TAG_T(t)>(c, gy, k, gx, pd); });
     }
     return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(c, 1, nullptr, gy, k, gx, nullptr); });
@@ -539,6 +549,7 @@ int km_filter2d_bwd_kernel(const void* gy, const void* x, void* gk, int B, int C
     KM_REQUIRE(gy && x && gk, "km_filter2d_bwd_kernel: null pointer");
     if (!km_config().sep_lds && km_filter2d_fast_supported(c, x, gy))  // one pass instead of kH*kW
         return km_filter2d_fast_tapgrad_run(c, gy, x, (double*)gk);
+    if (!km_config().sep_lds && km_filter2d_tiled_supported(c)) return km_filter2d_tiled_tapgrad_run(c, gy, x, (double*)gk);  // one pass, taps on lanes
     return km_dispatch_dtype<float, double, km_bf16, km_f16>(dtype, -1, [&](auto t) { return km_full_run<KM_TAG_T(t)>(c, 2, x, gy, nullptr, nullptr, (double*)gk); });
 }
 

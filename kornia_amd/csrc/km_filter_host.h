@@ -27,6 +27,15 @@ int km_filter2d_fast_tapgrad_run(const KmFilterCall& c, const void* gy, const vo
 int km_filter2d_fast_supported(const KmFilterCall& c, const void* x, const void* y);
 int km_filter2d_fast_run(const KmFilterCall& c, const void* x, const void* k, void* y, int border, int flip);
 
+// LDS budget of one workgroup of the LDS kernels of km_filter.hip and km_filter2d_tiled.hip
+#define KM_LDS_LIMIT (64 * 1024)
+
+// LDS-tiled full kH x kW kernels for what the register-tiled ones leave out, up to 31 x 31 (km_filter2d_tiled.hip): forward (flip = 0), the
+// zero-extended correlation with the rotated taps (flip = 1: the adjoint of 'valid' and constant padding, the interior of the others), tap gradient
+int km_filter2d_tiled_supported(const KmFilterCall& c);
+int km_filter2d_tiled_run(const KmFilterCall& c, const void* x, const void* k, void* y, int flip);
+int km_filter2d_tiled_tapgrad_run(const KmFilterCall& c, const void* gy, const void* x, double* gk);
+
 // register-tiled fast path for small square odd kernels (km_blur_fast.hip)
 int km_blur_fast_supported(const KmFilterCall& c, const void* x, const void* y);
 int km_blur_fast_bwd_supported(const KmFilterCall& c, const void* gy, const void* gx);

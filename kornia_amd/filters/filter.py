@@ -3,6 +3,13 @@
 Reference: kornia/filters/filter.py:54-152 (filter2d), :155-207 (filter2d_separable), :31-51
 (_compute_padding).  No padded copy is materialised and the separable case runs both passes in
 ONE launch with the intermediate held in LDS.  Differentiable wrt the input and the kernel(s).
+
+Which kernel a dense ``filter2d`` call takes (forward, input gradient and tap gradient alike; the results do not depend on it):
+  * 'same', square odd 3 / 5 / 7, W % 4 == 0, 16-byte aligned, not float64: the register-tiled kernels (csrc/km_filter2d_fast.hip);
+  * everything else up to 31 x 31 - larger, rectangular, even-sided, 1 x k / k x 1, 'valid', float64, any width or alignment: the
+    LDS-tiled kernels (csrc/km_filter2d_tiled.hip); an input gradient under reflect / replicate / circular padding whose image is not
+    larger than twice the pad + 1 keeps the generic adjoint;
+  * beyond 31 taps along an axis, and under the launch-policy key ``sep_lds = 1``: the generic per-pixel kernels (csrc/km_filter.hip).
 """
 from __future__ import annotations
 
@@ -172,6 +179,9 @@ def filter2d(
 
     ``border_type``: ``'constant' | 'reflect' | 'replicate' | 'circular'`` (for ``padding='same'``);
     ``padding='valid'`` shrinks the output to (H-kH+1, W-kW+1); ``normalized`` L1-normalises the kernel.
+
+    Kernels up to 31 x 31 run on tiled kernels (register tiles for aligned square 3 / 5 / 7 'same' calls, LDS tiles for every other
+    shape, padding and dtype), larger ones on the generic per-pixel kernels; see the module header.  The result is the same either way.
     """
     _validate(input, kernel, ["B", "H", "W"], border_type, padding, behaviour)
     N.require_device(input, "input")
