@@ -1030,6 +1030,19 @@ static bool km_fwd_cubic_try(const KmWarpArgs<T>& a, hipStream_t s) {
     else return km_warp_fwd_cubic_try_any(a, CM, s) != 0;
 }
 
+// the LDS box forward for bilinear + border / reflection / fill (km_warp_box_pad.hip) where it exists: matrices, fp32 compute; under
+// KM_WARP_FWD_ALGO=generic / rows these paddings keep the per-pixel kernel (A/B timing)
+template <typename T, int CM>
+static bool km_fwd_box_pad_try(const KmWarpArgs<T>& a, hipStream_t s) {
+    if constexpr (CM == KM_COORD_GRID || sizeof(typename KmTraits<T>::R) != sizeof(float)) return false;
+    else {
+        const int algo = km_config().warp_fwd_algo;  // 0 default, 3 "box"
+        // (an output with fewer pixels than the source: a map that minifies, whose boxes would not fit - km_warp_fwd_lean_launch's rule)
+        const bool shrinks = (uint64_t)a.g.H * (uint64_t)a.g.W * 10u > (uint64_t)a.g.h * (uint64_t)a.g.w * 13u;
+        return (algo == 3 || (algo == 0 && !shrinks)) && km_warp_fwd_box_pad_try_any(a, CM, s) != 0;
+    }
+}
+
 template <typename T, int CM, int INTERP>
 static int km_warp_launch(bool bwd, const KmWarpArgs<T>& a, hipStream_t s) {
     if (bwd)
@@ -1043,6 +1056,7 @@ static int km_warp_launch(bool bwd, const KmWarpArgs<T>& a, hipStream_t s) {
             hipLaunchKernelGGL((km_warp_fwd_bz_kernel<T, CM, 1>), dim3(a.nblocks), dim3(256), 0, s, a);
         else
             hipLaunchKernelGGL((km_warp_fwd_bz_kernel<T, CM, 0>), dim3(a.nblocks), dim3(256), 0, s, a);
+    } else if (INTERP == KM_INTERP_BILINEAR && a.g.pad != KM_PAD_ZEROS && km_fwd_box_pad_try<T, CM>(a, s)) {
     } else if (INTERP == KM_INTERP_BICUBIC && !km_fwd_generic_forced() && km_fwd_cubic_try<T, CM>(a, s)) {
     } else
         hipLaunchKernelGGL((km_warp_fwd_kernel<T, CM, INTERP>), dim3(a.nblocks), dim3(256), 0, s, a);

@@ -45,6 +45,11 @@ int km_warp_fwd_cubic_try_any(const KmWarpArgs<float>& a, int coord_mode, hipStr
 int km_warp_fwd_cubic_try_any(const KmWarpArgs<km_bf16>& a, int coord_mode, hipStream_t s);
 int km_warp_fwd_cubic_try_any(const KmWarpArgs<km_f16>& a, int coord_mode, hipStream_t s);
 
+// km_warp_box_pad.hip: the LDS box forward for bilinear + border / reflection / fill; launches and returns 1 when it takes the case, 0 otherwise
+int km_warp_fwd_box_pad_try_any(const KmWarpArgs<float>& a, int coord_mode, hipStream_t s);
+int km_warp_fwd_box_pad_try_any(const KmWarpArgs<km_bf16>& a, int coord_mode, hipStream_t s);
+int km_warp_fwd_box_pad_try_any(const KmWarpArgs<km_f16>& a, int coord_mode, hipStream_t s);
+
 // km_warp_bwd_tiled.hip: owner-computes grad_src for bilinear + zeros / fill
 int km_warp_bwd_tiled_supported(const KmWarpCall& c);
 int km_warp_bwd_tiled_dims_ok(const KmWarpCall& c);
